@@ -18,11 +18,21 @@ With --gpus N (configs 2/3/5) every rank denoises its own sample of the same siz
 at sample granularity); the only collective is the RCCL all-reduce of the 16 x Q transition-count
 matrix (accumulateTrans, R/errorModels.R:462-471), inside the timed region.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with, besides the contract's keys:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what that line's headline needs: it draws
+the inputs, warms up, times --steps steps, writes the last step's outputs (--dump-outputs DIR) and prints the line.  With --full
+it also measures, besides the contract's keys:
   roofline        dominant kernel of a fully event-timed pass (DADA2HIP_PROFILE=1: every launch timed, nothing
                   extrapolated): algorithmic work / measured duration vs the guide's peak and the measured peak
   cpu_baseline    the reference's own C++ (oracle/_ref: -O2 as R builds it, and -O3) on this box's host cores
   resident        the same pass on a sample already resident in HBM (what selfConsist passes 2..n cost)
+  (config 3)      the selfConsist loop, the configs[1] / [3] / [4] sub-records and the bimera table
+Without --full these keys are null.
+
+--dump-outputs DIR writes what the last timed step returned to its caller - the six objects of each boundary call - as
+DIR/<name>.npy in float64 (integers exact, letters as their byte values, NA / NaN and infinities as 0 with a
+<name>_nonfinite.npy marking them, so every value written is finite), at most 64 MB in all: beyond that a fixed, seeded
+sample of the rows of the longer arrays.  The inputs are seeded, so two builds run with the same arguments can be compared
+output for output.
 """
 import argparse
 import json
@@ -203,6 +213,62 @@ def sub_config4(api, local, args):
             "partitions_per_sample": [r.nclust for r in res], "comparisons": int(sum(r.stats["ncompare"] for r in res)), "gen_s": gen_s}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def result_arrays(r):
+    """The six objects one boundary call returns to its caller (opts.DadaResult), as float64 arrays by name: integers exactly
+    (NA_INTEGER included), letters as their byte values, the partitions' sequences as rows of byte values padded with -1.
+    Every value written is finite: a non-finite entry is written as 0 and <name>_nonfinite marks it (1 NaN / NA, 2 +Inf,
+    3 -Inf, 0 finite) - the same shape, so a row sample keeps the two aligned."""
+    def letters(strings):
+        width = max((len(x) for x in strings), default=0)
+        out = np.full((len(strings), width), -1.0)
+        for i, x in enumerate(strings):
+            out[i, : len(x)] = np.frombuffer(x.encode("ascii"), dtype=np.uint8)
+        return out
+
+    out = {}
+    for k, v in r.clustering.items():
+        out["clustering_" + k] = letters(v) if k == "sequence" else np.asarray(v, dtype=np.float64)
+    for k, v in r.birth_subs.items():
+        out["birth_subs_" + k] = letters(["".join(v)])[0] if k in ("ref", "sub") else np.asarray(v, dtype=np.float64)
+    for k in ("subqual", "clusterquals", "map", "pval"):
+        out[k] = np.asarray(getattr(r, k), dtype=np.float64)
+    for k in list(out):
+        a = out[k]
+        finite = np.isfinite(a)
+        if not finite.all():   # R's NA (NaN: e.g. the birth columns of the first partition) and infinities
+            out[k] = np.where(finite, a, 0.0)
+            out[k + "_nonfinite"] = np.select([np.isnan(a), a == np.inf, a == -np.inf], [1.0, 2.0, 3.0], 0.0)
+    return out
+
+
+def dump_outputs(results, outdir, prefix="", budget=DUMP_BUDGET_BYTES):
+    """Write result_arrays() of every result (one per sample: prefix sample<i>_ when there are several) to outdir/<name>.npy.
+    Over the budget, every array longer than 1 024 rows keeps the same fraction of its rows, drawn with a fixed seed (sorted):
+    the same rows on every run whose outputs have the same shapes."""
+    arrays = {}
+    for i, r in enumerate(results):
+        pre = prefix + (f"sample{i}_" if len(results) > 1 else "")
+        arrays.update({pre + k: v for k, v in result_arrays(r).items()})
+    total = sum(a.nbytes for a in arrays.values())
+    sampled = []
+    if total > budget:
+        small = sum(a.nbytes for a in arrays.values() if a.shape[0] <= 1024)
+        frac = max(0.0, (budget - small) / max(1, total - small))
+        for k, a in arrays.items():
+            if a.shape[0] > 1024:
+                keep = max(1, int(a.shape[0] * frac))
+                rows = np.sort(np.random.default_rng(20260925).choice(a.shape[0], size=keep, replace=False))
+                arrays[k] = a[rows]
+                sampled.append(k)
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), np.ascontiguousarray(a))
+    return {"dir": outdir, "arrays": len(arrays), "bytes": int(sum(a.nbytes for a in arrays.values())), "sampled": sampled}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -229,6 +295,10 @@ def main():
     ap.add_argument("--gen-only", action="store_true", help="draw this configuration's synthetic samples into the input cache and exit "
                     "(no GPU touched: the default line starts these for its sub-records while it measures the headline)")
     ap.add_argument("--gen-sample", type=int, default=-1, help="with --gen-only --config 4: only this sample of the eight")
+    ap.add_argument("--full", action="store_true", help="also measure what lies beside the headline: resident pass, event-timed "
+                    "profile pass + rooflines, CPU baseline with its parity check, the sub-records of config 3 (several minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the arrays the last timed step returned as "
+                    "DIR/<name>.npy (float64, at most 64 MB: a seeded sample of the rows beyond that)")
     args = ap.parse_args()
     if args.gen_only:
         if args.gen_sample >= 0:   # one sample of configs[3]'s eight = what rank `gen_sample` of 8 draws
@@ -261,8 +331,8 @@ def main():
     from dada2_amd import api
     from dada2_amd.opts import DadaOpts
 
-    extras = (args.config == 3 and world == 1 and not args.selfconsist and not args.no_extras and not args.deep and not args.shard
-              and not args.uniques)
+    extras = (args.full and args.config == 3 and world == 1 and not args.selfconsist and not args.no_extras and not args.deep
+              and not args.shard and not args.uniques)
     gens = []
     t0 = time.time()
     dereps, inputs, err, mine, c = make_inputs(args.config, args, rank)
@@ -345,6 +415,11 @@ def main():
         total_uniques = n_local
         per_rank = [{"rank": 0, "ms_per_step_own_wall": dt_rank / args.steps * 1e3, "samples": len(mine), "ms_allreduce_per_step": 0.0}]
 
+    dumped = None
+    if args.dump_outputs:   # what the last timed step returned, before anything else runs
+        dumped = dump_outputs(results, args.dump_outputs, prefix=f"rank{rank}_" if world > 1 else "",
+                              budget=DUMP_BUDGET_BYTES // world)
+
     if rank == 0:
         res, d = results[0], dereps[0]
         st = res.stats
@@ -353,7 +428,8 @@ def main():
 
         # ---- secondary: the same pass on a resident sample + a fully event-timed pass for the roofline --------------
         resident, prof, saturated = None, None, None
-        if not args.selfconsist and not args.shard:
+        roofline = other = None
+        if args.full and not args.selfconsist and not args.shard:
             smp = api.Sample(inputs[0], None, None, None, device=local)
             smp.run(err, opts)
             tr0 = time.perf_counter()
@@ -370,9 +446,10 @@ def main():
                 saturated = nw_saturated(smp, err, opts) if args.config != 5 else None   # (long reads run k_nw_adw)
             smp.close()
         pst = prof or st
-        ranked = rooflines(pst, L, band, args.config, d.nraw if prof else 0)
-        roofline, other = ranked[0], ranked[1:]
-        if prof is None:
+        if args.full:
+            ranked = rooflines(pst, L, band, args.config, d.nraw if prof else 0)
+            roofline, other = ranked[0], ranked[1:]
+        if args.full and prof is None:
             # without the event-timed pass the library only times a sample of the launches: no per-launch figure is claimed
             for r in ranked:
                 for k in ("achieved", "frac", "frac_of_measured_peak", "avg_launch_ms", "kernel_ms"):
@@ -386,7 +463,7 @@ def main():
         if extras:
             gens = start_generators([["--config", "2", "--deep"], ["--config", "5"], ["--config", "4"]])
         cpu = None
-        if not args.no_cpu_baseline and world == 1 and not args.selfconsist and not args.shard:
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.selfconsist and not args.shard:
             cpu = cpu_baseline(d, err, opts, args, res, gpu_cmp_per_s=st["ncompare"] * len(inputs) * world * args.steps / dt)
 
         # ---- sub-records of the default line: BASELINE configs[2]'s selfConsist loop on this very sample, and a workload
@@ -394,7 +471,8 @@ def main():
         secondary = plain2 = None
         bimera = None
         sub5 = sub4 = None
-        if args.config == 3 and world == 1 and not args.selfconsist and not args.no_extras and not args.deep and not args.shard:
+        if (args.full and args.config == 3 and world == 1 and not args.selfconsist and not args.no_extras and not args.deep
+                and not args.shard):
             tm = []
             t_sc = time.perf_counter()
             sc_passes = []
@@ -471,6 +549,8 @@ def main():
             "samples_in_flight_per_gpu": (min(args.inflight, len(inputs)) if len(inputs) > 1 else 1),
             "collective": "one all-reduce(sum) of the 16 x %d int64 transition counts per step (RCCL; accumulateTrans, R/errorModels.R:462-471)" % maxcol if world > 1 else None,
             "gen_s": t_gen,
+            "full": bool(args.full),
+            "outputs_dumped": dumped,
         }
         print(json.dumps(out))
     if shard_smp is not None:

@@ -5,9 +5,14 @@ uniques.  The generator follows the survey's recipe: families of true variants d
 from one ancestor, Zipf abundances, a linear quality ramp with Gaussian jitter, and
 substitution errors drawn from the error matrix itself (so the data are self-consistent
 with the model), then dereplication exactly as ``derepFastq`` would do it
-(dada2_amd/io.py).  Everything is numpy-vectorised so 10^6 uniques take ~a minute.
+(dada2_amd/io.py).  Everything is numpy-vectorised, and each chunk's element-wise work runs on a few
+threads while the next chunk is drawn: 10^6 uniques take 10-15 s.  The random stream is consumed in a
+fixed order, so a seed gives the same sample bit for bit however the work is scheduled.
 """
 from __future__ import annotations
+
+import os
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -80,8 +85,10 @@ def _derep_codes(codes: np.ndarray, lens: np.ndarray, quals: np.ndarray) -> Dere
         lex = np.arange(U)
     order = lex[np.argsort(-counts[lex], kind="stable")]   # (-abundance, sequence): stable R order()
     mean = mean[order]
-    for k, u in enumerate(order):
-        mean[k, ulen[u]:] = np.nan
+    short = ulen[order] < L
+    if short.any():
+        rows = np.flatnonzero(short)
+        mean[rows] = np.where(np.arange(L)[None, :] >= ulen[order][rows][:, None], np.nan, mean[rows])
     rank = np.empty(U, dtype=np.int64)
     rank[order] = np.arange(U)
     return Derep([seqs[u] for u in order], counts[order].astype(np.int32), mean, rank[inv].astype(np.int32))
@@ -101,53 +108,84 @@ def make_sample(err: np.ndarray, n_uniques: int, L: int = 250, G: int = 256, see
     err = np.asarray(err, dtype=np.float64)
     Q = err.shape[1]
     ramp = np.linspace(q_hi, q_lo, L)
-    all_codes, all_lens, all_q = [], [], []
-    seen = 0
-    seen_keys = set()
-    while True:
-        g = rng.choice(G, size=chunk, p=w)
-        codes = tv[g].copy()
-        lens = tl[g].copy()
-        q = np.clip(np.rint(ramp[None, :] + rng.normal(0.0, q_sd, size=(chunk, L))), 2, min(q_max, Q - 1)).astype(np.uint8)
-        # substitution errors: P(b -> b') = err[4b+b', q]
-        u = rng.random(size=(chunk, L))
-        b = codes.astype(np.int64)
-        cum = np.zeros((chunk, L))
-        newc = codes.copy()
-        done = np.zeros((chunk, L), dtype=bool)
+    qcap = min(q_max, Q - 1)
+    # substitution errors: P(b -> b') = err[4b+b', q].  A base b read at quality q becomes (b + k) & 3 for the first k in 1..3
+    # whose running sum err[4b + (b+1)&3, q] + ... + err[4b + (b+k)&3, q] exceeds its uniform draw; the sums are tabulated
+    # once per (b, q), added in that same order
+    cut = np.zeros((3, 4 * Q))
+    for b in range(4):
+        c = np.zeros(Q)
         for k in range(1, 4):
-            tgt = (b + k) & 3
-            cum += err[4 * b + tgt, q]
-            hit = (~done) & (u < cum)
-            newc[hit] = tgt[hit].astype(np.uint8)
-            done |= hit
-        codes = newc
+            c = c + err[4 * b + ((b + k) & 3)]
+            cut[k - 1, b * Q:(b + 1) * Q] = c
+    nthreads = max(1, min(8, os.cpu_count() or 1))
+
+    def draw():
+        """One chunk's random draws, in stream order: truth, quality noise, substitution draws, then the per-read indel draws
+        (their positions depend on the read lengths only, so they are drawn here and applied by build())."""
+        g = rng.choice(G, size=chunk, p=w)
+        lens = tl[g].copy()
+        noise = rng.normal(0.0, q_sd, size=(chunk, L))
+        u = rng.random(size=(chunk, L))
+        dels, ins = [], []
         if indel_rate > 0:
             # rare single-base deletions (exercise the band); applied per read, at most one
             has = rng.random(chunk) < indel_rate * lens
             for r in np.nonzero(has)[0]:
-                p = int(rng.integers(1, lens[r] - 1))
-                codes[r, p:-1] = codes[r, p + 1:]
-                q[r, p:-1] = q[r, p + 1:]
+                dels.append((r, int(rng.integers(1, lens[r] - 1))))
                 lens[r] -= 1
         if ins_rate > 0:
             # rare single-base insertions (a read at full length keeps its length: its last base falls off)
             has = rng.random(chunk) < ins_rate * lens
             for r in np.nonzero(has)[0]:
-                p = int(rng.integers(1, lens[r] - 1))
-                codes[r, p + 1:] = codes[r, p:-1].copy()
-                q[r, p + 1:] = q[r, p:-1].copy()
-                codes[r, p] = rng.integers(0, 4)
+                ins.append((r, int(rng.integers(1, lens[r] - 1)), rng.integers(0, 4)))
                 lens[r] = min(L, lens[r] + 1)
+        return g, lens, noise, u, dels, ins
+
+    def build(g, lens, noise, u, dels, ins):
+        """The reads of one drawn chunk, and the distinct reads among them."""
+        codes = tv[g].copy()
+        q = np.empty((chunk, L), dtype=np.uint8)
+
+        def rows(r0, r1):   # element-wise on a block of reads (numpy releases the GIL: the blocks run side by side)
+            qb = np.clip(np.rint(ramp[None, :] + noise[r0:r1]), 2, qcap).astype(np.uint8)
+            q[r0:r1] = qb
+            cb = codes[r0:r1]
+            idx = cb.astype(np.intp) * Q + qb
+            ub = u[r0:r1]
+            out = np.where(ub < cut[2].take(idx), (cb + 3) & 3, cb)
+            out = np.where(ub < cut[1].take(idx), (cb + 2) & 3, out)
+            codes[r0:r1] = np.where(ub < cut[0].take(idx), (cb + 1) & 3, out)
+
+        edges = np.linspace(0, chunk, min(nthreads, chunk) + 1).astype(int)
+        with ThreadPoolExecutor(len(edges) - 1) as ex:
+            list(ex.map(rows, edges[:-1], edges[1:]))
+        for r, p in dels:
+            codes[r, p:-1] = codes[r, p + 1:]
+            q[r, p:-1] = q[r, p + 1:]
+        for r, p, base in ins:
+            codes[r, p + 1:] = codes[r, p:-1].copy()
+            q[r, p + 1:] = q[r, p:-1].copy()
+            codes[r, p] = base
         pad = np.arange(L)[None, :] >= lens[:, None]
         codes[pad] = 255
         q[pad] = 0
-        all_codes.append(codes); all_lens.append(lens); all_q.append(q)
         keys = np.ascontiguousarray(codes).view(np.dtype((np.void, L))).ravel()
-        seen_keys.update(np.unique(keys).tolist())
-        seen = len(seen_keys)
-        if seen >= n_uniques:
-            break
+        return codes, lens, q, np.unique(keys).tolist()
+
+    all_codes, all_lens, all_q = [], [], []
+    seen_keys = set()
+    with ThreadPoolExecutor(1) as builder:
+        pending = builder.submit(build, *draw())
+        while True:
+            ahead = draw()   # the next chunk of the stream, drawn while the last one is built (unused if that one was enough)
+            codes, lens, q, keys = pending.result()
+            all_codes.append(codes); all_lens.append(lens); all_q.append(q)
+            seen_keys.update(keys)
+            if len(seen_keys) >= n_uniques:
+                break
+            pending = builder.submit(build, *ahead)
+        del ahead
     codes = np.concatenate(all_codes); lens = np.concatenate(all_lens); q = np.concatenate(all_q)
     d = _derep_codes(codes, lens, q)
     if d.nraw > n_uniques:  # drop the rarest (last) uniques and the reads that map to them

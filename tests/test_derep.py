@@ -13,9 +13,10 @@ import pytest
 from dada2_amd import api
 from oracle import derep as dio
 from dada2_amd._lib import Dada2HipError
-from helpers import load_input
+from helpers import GOLDEN, load_input
 
-REF_EXT = "/root/reference/inst/extdata"
+# the reference package's own FASTQ fixtures (its inst/extdata), stored beside the goldens derived from them
+REF_EXT = GOLDEN
 
 
 def write_fastq(path, seqs, quals, crlf=False, gz=False):
@@ -103,16 +104,12 @@ def test_errors_of_the_reference_are_kept(tmp_path):
 
 
 FIXTURES = ["sam1F", "sam1R", "sam2F", "sam2R", "samPB"]
-needs_fixtures = pytest.mark.skipif(not os.path.isdir(REF_EXT), reason="reference fixtures not on this machine")
 
 
-@needs_fixtures
 @pytest.mark.parametrize("name", FIXTURES)
 def test_reference_fixtures_give_the_golden_inputs(name):
     """Byte for byte: sequences, abundances and the integer per-position quality sums the goldens hold (the means the
     library returns are sum / abundance in fp64: comparing sums is the stricter test)."""
-    import numpy as np
-    from helpers import GOLDEN
     got = api.derep_fastq(f"{REF_EXT}/{name}.fastq.gz")
     z = np.load(os.path.join(GOLDEN, name + ".input.npz"))
     assert got.seqs == [str(s) for s in z["seqs"]]
@@ -131,14 +128,12 @@ def test_reference_fixtures_give_the_golden_inputs(name):
         np.testing.assert_array_equal(got.map, np.load(os.path.join(GOLDEN, "sam1_maps.npz"))[name])
 
 
-@needs_fixtures
 def test_known_unique_counts_of_the_reference_fixtures():
     """SURVEY.md §4/§6 (from the reference's own documentation run): sam1F.fastq.gz holds 1 500 reads in 896 uniques."""
     d = api.derep_fastq(f"{REF_EXT}/sam1F.fastq.gz")
     assert d.nraw == 896 and int(d.abundances.sum()) == 1500 and len(d.map) == 1500
 
 
-@needs_fixtures
 @pytest.mark.parametrize("name", FIXTURES)
 def test_uniques_and_order_against_coreutils(name, tmp_path):
     """An implementation nobody here wrote: `sort | uniq -c` in the C locale, then a stable sort by count, is exactly

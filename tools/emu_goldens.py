@@ -1,7 +1,8 @@
 import sys, time, os
-sys.path[:0]=['/root/repo','/root/repo/tests']
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0]=[ROOT, os.path.join(ROOT, 'tests')]
 from dada2_amd import _lib
-sys.path.insert(0, '/root/repo/tests/emu'); import build as emu_build; _lib.LIB_PATH = emu_build.build()
+sys.path.insert(0, os.path.join(ROOT, 'tests', 'emu')); import build as emu_build; _lib.LIB_PATH = emu_build.build()
 from helpers import case_inputs, assert_results_equal, WHOLE_PATH_CASES
 from dada2_amd import api
 import os
