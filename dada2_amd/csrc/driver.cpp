@@ -1804,7 +1804,7 @@ struct Run {
       launch2_screen_multi(E2, stq);
       ev_end(rec.ev_screen);
       launch2_batch_lists(E2, stq);
-      const NwBatch nb{&v2_ctl.p->nalign, v2_blistn.p, v2_blist.p, v2_ctl.p->acentre, &v2_ctl.p->abuf, E2.C.Npad, v2_bretry.p, v2_bretryn.p, v2_retrytot.p};
+      const NwBatch nb{&v2_ctl.p->nalign, v2_blistn.p, v2_blist.p, v2_ctl.p->acentre, &v2_ctl.p->abuf, E2.C.Npad, v2_bretry.p, v2_bretryn.p, v2_retrytot.p, &v2_ctl.p->fast_off};
       launch_gapless_batch(s->D, nb, ap, s->d_err.p, v2_lamB.p, v2_hamB.p, &v2_ctl.p->state, stq);
       rec.ev_nw = ev_begin(EV_NW, profile_all, /*spec=*/true);
       launch_nw_ad(s->D, -1, nullptr, nullptr, nullptr, 0, nullptr, nullptr, ap, s->d_err.p, v2_lamB.p, v2_hamB.p, nullptr, 0, 0, nullptr, stq,
@@ -1842,7 +1842,7 @@ struct Run {
     launch2_screen_multi(E2P, st2, /*beside_tail=*/v3_pf_lowreg);
     ev_end(ev);
     launch2_batch_lists(E2P, st2);
-    const NwBatch nb{&pc->nalign, v3_pf_blistn.p, v3_pf_blist.p, pc->acentre, &pc->abuf, E2.C.Npad, v3_pf_bretry.p, v3_pf_bretryn.p, v2_retrytot.p};
+    const NwBatch nb{&pc->nalign, v3_pf_blistn.p, v3_pf_blist.p, pc->acentre, &pc->abuf, E2.C.Npad, v3_pf_bretry.p, v3_pf_bretryn.p, v2_retrytot.p, &pc->fast_off};
     launch_gapless_batch(S2, nb, ap, s->d_err.p, v2_lamB.p, v2_hamB.p, &pc->state, st2);
     ev = ev_begin(EV_PF_NW, profile_all, false, false, st2);
     launch_nw_ad(S2, -1, nullptr, nullptr, nullptr, 0, nullptr, nullptr, ap, s->d_err.p, v2_lamB.p, v2_hamB.p, nullptr, 0, 0, nullptr, st2,
@@ -2238,7 +2238,7 @@ struct Run {
       ev_end(rec.ev_screen);
       // ... its survivors through the aligner, all batch positions in one launch (both no-ops on a cache hit) ...
       launch2_batch_lists(E2, stq);
-      const NwBatch nb{&v2_ctl.p->nalign, v2_blistn.p, v2_blist.p, v2_ctl.p->acentre, &v2_ctl.p->abuf, E2.C.Npad, v2_bretry.p, v2_bretryn.p, v2_retrytot.p};
+      const NwBatch nb{&v2_ctl.p->nalign, v2_blistn.p, v2_blist.p, v2_ctl.p->acentre, &v2_ctl.p->abuf, E2.C.Npad, v2_bretry.p, v2_bretryn.p, v2_retrytot.p, &v2_ctl.p->fast_off};
       launch_gapless_batch(s->D, nb, ap, s->d_err.p, v2_lamB.p, v2_hamB.p, &v2_ctl.p->state, stq);
       rec.ev_nw = ev_begin(EV_NW, profile_all, /*spec=*/true);
       launch_nw_ad(s->D, -1, nullptr, nullptr, nullptr, 0, nullptr, nullptr, ap, s->d_err.p, v2_lamB.p, v2_hamB.p, nullptr, 0, 0, nullptr, stq,

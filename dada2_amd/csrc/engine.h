@@ -232,6 +232,7 @@ struct NwBatch {
   int32_t *retry_list = nullptr;
   int32_t *retry_n = nullptr;
   unsigned long long *fast_ctl = nullptr;   // [0] pairs handed over so far, [1] pairs the pass has looked at, [2] != 0: the pass is off (Eng2::fast_ctl)
+  const int32_t *fast_off = nullptr;        // != 0: the pass is off for THIS compare (Ctl2::fast_off of the control block that planned it)
 };
 void launch_gapless_batch(const SampleDev &S, const NwBatch &b, const AlignParams &ap, const double *d_err, double *d_lambda,
                           uint32_t *d_ham, const int32_t *d_stop_dev, hipStream_t st);
@@ -357,6 +358,10 @@ struct Ctl2 {
   // ended in time / that ended with the launch left; centres prefetched
   int32_t pf_hits, pf_spins, pf_exits, pf_centres;
   unsigned long long pf_mask;   // bit b: batch buffer b was filled by a prefetch
+  // the aligner's pointer-free pass is off for the compare in flight (NwBatch::fast_off): latched by k2_batch_lists from the run's
+  // counters in front of each compare, read by every launch of that compare.  The counters are shared by both streams and may
+  // change while a compare runs; this word is the compare's own
+  int32_t fast_off, fast_off_pad;
 };
 
 // Results of the batch compares, kept until their centre's round comes (or the batch buffer is recycled): the class, 2 bits

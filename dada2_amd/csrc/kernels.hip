@@ -477,9 +477,12 @@ struct NwArgs {
   int32_t *retry_n;
   // fast_ctl[0] = pairs handed over so far in this run, [1] = pairs the pointer-free pass has looked at, [2] != 0: the pass is OFF
   // for the rest of the run - it handed more than a quarter of its pairs over (reads with indels everywhere: PacBio-style), so two
-  // sweeps cost more than one.  Decided by k2_batch_lists in front of each compare; while off the FAST launch returns at once and
-  // the full kernel, launched on the retry lists, works through the batch's OWN lists instead (alt_list / alt_n)
+  // sweeps cost more than one.  k2_batch_lists decides from these run-wide words in front of each compare and latches the
+  // decision into *fast_off, the compare's own word: the words above are shared by the compares of both streams and may flip
+  // while this one runs, so every block of every launch of the compare reads *fast_off only.  While off the FAST launch returns
+  // at once and the full kernel, launched on the retry lists, works through the batch's OWN lists instead (alt_list / alt_n)
   unsigned long long *fast_ctl;
+  const int32_t *fast_off;
   const int32_t *alt_list;
   const int32_t *alt_n;
 };
@@ -1071,8 +1074,8 @@ __global__ __launch_bounds__(256, 4) void k_nw_ad(NwArgs a, const int32_t *__res
     if (batch) {
       const int nb = *a.batch_on;
       if (nb <= 0) return;
-      if (a.fast_ctl) {
-        const bool off = a.fast_ctl[2] != 0ull;
+      if (a.fast_off) {
+        const bool off = *a.fast_off != 0;
         if (FAST) {
           if (off) return;
           if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -1502,10 +1505,10 @@ __global__ __launch_bounds__(256) void k_ad_product(const uint16_t *__restrict__
                                                     const double *__restrict__ err, int nerr, double *__restrict__ lam,
                                                     const int32_t *__restrict__ stop_dev, const int32_t *__restrict__ batch_on,
                                                     const int32_t *__restrict__ batch_n, int slots_per_slice,
-                                                    const unsigned long long *__restrict__ fast_ctl = nullptr, const int32_t *__restrict__ alt_n = nullptr) {
+                                                    const int32_t *__restrict__ fast_off = nullptr, const int32_t *__restrict__ alt_n = nullptr) {
   extern __shared__ double s_err[];
   if (stop_dev && *stop_dev != 0) return;
-  if (fast_ctl && alt_n && fast_ctl[2] != 0ull) batch_n = alt_n;   // (the pointer-free pass is off: the launch in front worked on the batch's own lists)
+  if (fast_off && alt_n && *fast_off != 0) batch_n = alt_n;   // (the pointer-free pass is off for this compare: the launch in front worked on the batch's own lists)
   if (batch_on) {   // batch mode: the launch's work slots are known on the device only (the lists' lengths, as k_nw_ad counts them)
     const int nb = *batch_on;
     if (nb <= 0) return;
@@ -1566,7 +1569,7 @@ void launch_nw_ad(const SampleDev &S, int centre, const int32_t *d_chunk_centre,
   const bool def = !homo && ap.match == 5 && ap.mismatch == -4 && ap.gap == -8 && ap.sentinel == -32760;
   // a batch compare on the default scores: first the pointer-free pass over the batch's lists (k_nw_ad<.., FAST>), then the full
   // kernel over the pairs that pass could not finish (its retry lists: usually a few per cent of the pairs, often none)
-  const bool fast = batch && def && batch->retry_list && batch->retry_n && knobs().ad_fast != 0 && a.moves_stride == 0;
+  const bool fast = batch && def && batch->retry_list && batch->retry_n && batch->fast_off && knobs().ad_fast != 0 && a.moves_stride == 0;
   // per (instance, device): the dynamic-LDS attribute belongs to the function ON a device
   auto set_lds = [&](const void *fn, std::atomic<size_t> (&done)[64]) {
     int dev_ = 0;
@@ -1590,17 +1593,17 @@ void launch_nw_ad(const SampleDev &S, int centre, const int32_t *d_chunk_centre,
     else if (def) { if (G.edge) D2_LAUNCH_AD(GLV, true, true, false, false); else D2_LAUNCH_AD(GLV, true, false, false, false); } \
     else { if (G.edge) D2_LAUNCH_AD(GLV, false, true, false, false); else D2_LAUNCH_AD(GLV, false, false, false, false); }   \
   } while (0)
-  auto product = [&](const int32_t *list_n, const unsigned long long *fctl = nullptr, const int32_t *alt_n = nullptr) {   // the products of what a launch aligned (its work slots: ids below the bound)
+  auto product = [&](const int32_t *list_n, const int32_t *foff = nullptr, const int32_t *alt_n = nullptr) {   // the products of what a launch aligned (its work slots: ids below the bound)
     if (!(S.ad_foff && a.moves_stride == 0)) return;
     const int nerr = 16 * ap.ncol;
     long long bound = batch ? (long long)S.ad_fcap : (long long)((maxwork + (d_gl_work ? S.N : 0) + 4 * G.APW - 1) / (4 * G.APW) + 1) * 4 * G.APW;
     const int nscan = (int)std::min<long long>(bound, S.ad_fcap);
     const int pgrid = std::max(1, std::min((nscan + 255) / 256, 2048));
     hipLaunchKernelGGL(k_ad_product, dim3(pgrid), dim3(256), (size_t)nerr * 8, st, (const uint16_t *)S.ad_foff, (int)S.ad_fstride, S.ad_desc, nscan, d_err, nerr,
-                       d_lambda, d_stop_dev, batch ? batch->on : nullptr, list_n, 4 * G.APW, fctl, alt_n);
+                       d_lambda, d_stop_dev, batch ? batch->on : nullptr, list_n, 4 * G.APW, foff, alt_n);
   };
   if (fast) {
-    a.retry_list = batch->retry_list; a.retry_n = batch->retry_n; a.fast_ctl = batch->fast_ctl;
+    a.retry_list = batch->retry_list; a.retry_n = batch->retry_n; a.fast_ctl = batch->fast_ctl; a.fast_off = batch->fast_off;
     if (G.GL == 21) D2_LAUNCH_AD2(21, true);
     else if (G.GL == 32) D2_LAUNCH_AD2(32, true);
     else D2_LAUNCH_AD2(64, true);
@@ -1614,7 +1617,7 @@ void launch_nw_ad(const SampleDev &S, int centre, const int32_t *d_chunk_centre,
   else D2_LAUNCH_AD2(64, false);
 #undef D2_LAUNCH_AD2
 #undef D2_LAUNCH_AD
-  if (fast) product(batch->retry_n, batch->fast_ctl, batch->n);
+  if (fast) product(batch->retry_n, batch->fast_off, batch->n);
   else product(batch ? batch->n : nullptr);
 }
 

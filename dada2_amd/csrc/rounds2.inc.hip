@@ -710,8 +710,14 @@ __global__ __launch_bounds__(256) void k2_batch_lists(Eng2 E) {
   // (the retry lists of the aligner's pointer-free pass, which follows in the stream, start empty)
   if (blockIdx.x == 0 && threadIdx.x < KB_MAX && E.bretry_n) E.bretry_n[threadIdx.x] = 0;
   // ... and the pass is switched off for the rest of the run once it has handed more than a quarter of its pairs to the full
-  // kernel (a sweep without pointers costs about 0.8 of one with: beyond that two sweeps lose to one)
-  if (blockIdx.x == 0 && threadIdx.x == 0 && E.fast_ctl && E.fast_ctl[1] >= 2048ull && 4ull * E.fast_ctl[0] > E.fast_ctl[1]) E.fast_ctl[2] = 1ull;
+  // kernel (a sweep without pointers costs about 0.8 of one with: beyond that two sweeps lose to one).  The run's words are
+  // shared with the compare of the other stream, which may flip them at any time; what THIS compare's launches read is the
+  // decision latched here into its own control block (Ctl2::fast_off, NwBatch::fast_off)
+  if (blockIdx.x == 0 && threadIdx.x == 0 && E.fast_ctl) {
+    const bool off = E.fast_ctl[2] != 0ull || (E.fast_ctl[1] >= 2048ull && 4ull * E.fast_ctl[0] > E.fast_ctl[1]);
+    if (off) E.fast_ctl[2] = 1ull;
+    E.ctl->fast_off = off ? 1 : 0;
+  }
   __shared__ int s_cnt[2 * KB_MAX], s_base[2 * KB_MAX];
   const SampleDev &S = E.S;
   const uint16_t *bcls = E.C.bcls + (size_t)ctl->abuf * E.C.Npad;
