@@ -16,7 +16,6 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
-#include <deque>
 #include <exception>
 #include <mutex>
 #include <cmath>
@@ -336,11 +335,6 @@ void sample_create(dada2hip_sample *s, int32_t nraw, const char *const *seqs, co
   D.W2 = (((maxlen + 15) / 16) + 3) & ~3;
   D.LQ = (maxlen + 15) & ~15;
   D.LK = (std::max(maxlen - KMER_SIZE + 1, 1) + 7) & ~7;
-  {   // DADA2HIP_KORD_ALIGN=1: rows of k-mer records padded to 128-B cache lines (the screen's two 256-B reads per row then
-      // touch 2 lines each instead of 3).  Measured 2 % on the screen at 1e6 uniques for 3 % more memory: off by default.
-    const bool aligned = knobs().kord_align;
-    if (aligned) D.LK = (D.LK + 63) & ~63;
-  }
   D.HMAX = std::max(0, (maxlen - KMER_SIZE + 1) / (RANK_SAT + 1));
 
   // 2-bit packing on the host pool, straight into pinned memory (validates ACGT: R checks C_isACGT before the call,
@@ -592,7 +586,7 @@ struct BudKeyH { double p; uint32_t reads; uint32_t pad; };
 
 // below this many alignments in one launch the cooperative (anti-diagonal) kernel beats one-alignment-per-lane
 // (measured up to 1e6 alignments: 1M-unique pass 358 -> 349 ms; beyond 4e6 untested, the lane kernel takes over)
-#define COOP_MAX_BATCH (knobs().coop_max)
+constexpr int COOP_BATCH_LIMIT = 4000000;
 
 struct Run {
   dada2hip_sample *s;
@@ -657,7 +651,6 @@ struct Run {
 
   ~Run() {
     for (auto &e : evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    for (auto g : v2_graph) if (g) (void)hipGraphExecDestroy(g);
     for (auto e : v3_pf_ev) if (e) (void)hipEventDestroy(e);
   }
 
@@ -935,7 +928,7 @@ struct Run {
     spec_ev_nw = spec ? evn_i : -1;
     const int f = knobs().nw_kernel;
     const bool coop_ok = nw_ad_lds_bytes(D, ap) > 0 && nw_ad_lds_bytes(D, ap) <= 150 * 1024;
-    bool coop = coop_ok && (ci != 0 || N < COOP_MAX_BATCH);
+    bool coop = coop_ok && (ci != 0 || N < COOP_BATCH_LIMIT);
     if (f == NWK_LANE) coop = false;
     if (f == NWK_COOP && coop_ok) coop = true;
     // band windows too wide for the LDS-pointer kernel (ragged long reads): eight cells per lane, pointers in HBM
@@ -985,7 +978,7 @@ struct Run {
   std::vector<std::pair<uint64_t, int32_t>> replay_keys, replay_tmp;
   std::vector<int32_t> replay_order;
   void replay_moves(const int32_t *mv, int nm) {
-    const bool feed = v3_running && !lane_is_me();                  // (launches are the boundary thread's to send)
+    const bool feed = v3_running;
     if (feed && nm > 2048) v3_topup();
     // The reference pops the movers of one b_shuffle2 call partition by partition, each partition's from its LAST slot down
     // (cluster.cpp:241-262 walks r = nraw - 1 .. 0): by source partition ascending, then by the slot the unique holds now, descending.
@@ -1257,7 +1250,6 @@ struct Run {
   }
 
   void push_slot0() {   // only reachable when a slot-0 unique is not its partition's centre (unsorted input: plain mode)
-    if (lane_is_me()) throw RuntimeErr{DADA2HIP_ERR_RUNTIME, "dada2hip: internal error: a slot-0 member moved under the device-driven rounds"};
     std::vector<uint8_t> f(N, 0);
     for (auto &b : bi) if (!b.raw.empty()) f[b.raw[0]] = 1;
     D2_HIP(hipMemcpyAsync(P.slot0, f.data(), (size_t)N, hipMemcpyHostToDevice, s->stream));   // ordered with the evaluations
@@ -1465,13 +1457,11 @@ struct Run {
   bool v3_on = false;                 // this run's rounds go through k3_tail (else: the launch chains)
   int v3_depth = 1;                   // persistent launches kept in flight (DADA2HIP_V2_DEPTH)
   int v3_grid = 1;                    // its blocks (co-resident: at most one per CU)
-  int v3_bs = 1024;                   // threads per block
   long v3_enq = 0;                    // k3_tail launches enqueued (their ordinals are 1, 2, ...)
   long v3_ord_seen = 0;               // launch ordinal of the last consumed block
   DevBuf<PSync> v3_psync;
   DevBuf<int32_t> v3_lockbuf;         // Eng2::spec_lock_buf: per block, the locks an evaluation attempt has decided (published when it stands)
   int v3_lock_stride = 0;
-  bool v3_pf_lowreg = false;          // prefetch screens on the 80-register build of the screen kernel (the tail shares every CU with them)
   // ---- the next batch's compare under the tail: a second set of everything a batch compare works with ----
   bool v3_overlap = false;
   Eng2 E2P{};                         // argument block of the prefetch compare's kernels (ctl = the prefetch descriptor, own tables / lists / aligner scratch)
@@ -1537,7 +1527,7 @@ struct Run {
     {   // the tail's LDS mirror of the per-unique facts its sweeps ask for (Eng2::mirror_on): where the uniques one block sweeps fit it
       const long long per_group = 4096ll * std::max(1, v3_grid);
       const long long per_block = ((long long)N + per_group - 1) / per_group * 4096ll;
-      E2.mirror_on = (v3_on && K.v3_mirror != 0 && N < (1 << 24) && per_block <= (long long)tail_mirror_cap(s->device, v3_bs)) ? (K.v3_mirror == 2 ? 2 : 1) : 0;   // (2: test knob - every round ends with a comparison of the mirror with the arrays)
+      E2.mirror_on = (v3_on && K.v3_mirror != 0 && N < (1 << 24) && per_block <= (long long)tail_mirror_cap(s->device)) ? (K.v3_mirror == 2 ? 2 : 1) : 0;   // (2: test knob - every round ends with a comparison of the mirror with the arrays)
     }
     // grid barriers inside a persistent launch: XCD-hierarchical from 48 blocks on (rounds3.inc.hip::grid_sync; a small grid is
     // faster on the flat one).  (v3_grid is v3_setup's, which runs in front of every bind)
@@ -1574,14 +1564,13 @@ struct Run {
       E2P = E2; E2P.S = S2; E2P.ctl = v3_pfctl.p; E2P.C.tab8 = v3_pf_tab8.p; E2P.C.full = v3_pf_full.p; E2P.C.ord = v3_pf_ord.p; E2P.C.cbits = v3_pf_cbits.p;
       E2P.blist = v3_pf_blist.p; E2P.blist_n = v3_pf_blistn.p; E2P.bretry = v3_pf_bretry.p; E2P.bretry_n = v3_pf_bretryn.p; E2P.pf_on = 0; E2P.has_compare = 1;
     }
-    v2_drop_graph();                 // (captured launches hold the old argument block)
   }
   void v2_alloc(int max_clust) {
     const size_t n = (size_t)N;
     v2_nbuf = 64;   // 512 cached centres, 2 bytes x N each (r02l sweep: 64 buffers beat 32 by 2.5 % at 1M uniques)
     {   // a batch buffer holds class words and the aligner's results for KB_MAX centres: 98 bytes per unique.  At most an
         // eighth of the device's memory goes to the cache (64 buffers take 6.3 GB at 10^6 uniques).  hipDeviceTotalMem, not
-        // hipMemGetInfo: the latter is refused while ANOTHER host thread captures its round graph (dada2hip_run_multi).
+        // hipMemGetInfo: the latter is refused while another host thread of the process captures a stream.
       size_t total_b = 0;
       int dev_ = 0;
       (void)hipGetDevice(&dev_);
@@ -1669,43 +1658,28 @@ struct Run {
   void v3_setup(hipStream_t stq) {
     const Knobs &K = knobs();
     v3_on = !K.v2_tail_chain;
-    if (K.v2_graph) v3_on = false;                                      // (hipGraph replay is a property of the chains)
     if (v2_trace_seq >= 0 || K.v2_trace_on) v3_on = false;              // (the phase trace stamps the chains' kernels)
 
     v3_grid = tail_grid(N, s->device);
     if (K.v3_grid > 0) v3_grid = std::min(K.v3_grid, tail_grid(1 << 30, s->device));
     // refuse up front a grid the device cannot hold at once (the entry barrier would time out): the launch chains serve the run
     // The next batch's compare under the tail: on by default where batches are aligned ahead (not the long reads,
-    // which align at commit time) and the cache is deep enough to give a prefetch a buffer of its own.  The tail then runs on
-    // 512-thread blocks: half of every CU's registers stay free for the compare's kernels.
+    // which align at commit time) and the cache is deep enough to give a prefetch a buffer of its own.
     v3_overlap = v3_on && !v2_align_commit && v2_nbuf >= 4 && K.v3_overlap != 0 && N >= 2 && (active_runs(s->device).load() <= 1 || K.v3_overlap == 1);
-    // (1024-thread blocks: under the overlap the tail takes its CUs WHOLE - ceil(N / 4096) of them for a sample of up to half the
-    //  device, half of the device beyond that (below) - and the compares' kernels have the others to themselves.  Round 5 put
-    //  512-thread blocks beside the compares on every CU up to 5 10^5 uniques: the same time at 10^5 plain uniques (12.9 ms both),
-    //  and 38.3 against 33.9 ms on the deep 10^5 workload, profiles/r09h; DADA2HIP_V3_BLOCK=512 keeps that form for the tests)
-    v3_bs = K.v3_block == 512 ? 512 : 1024;
+    // Under the overlap the tail takes its CUs WHOLE (1024-thread blocks at 128 registers fill a CU's register file) - ceil(N / 4096)
+    // of them for a sample of up to half the device, HALF of the device beyond that - and the compares' kernels have the others to
+    // themselves at their full occupancy.  10^6 uniques, one box, median of nine with the XCD-hierarchical barrier: 128 x 1024
+    // 135.0-136.5 ms, 96 x 1024 139.3-141.6 (profiles/r08b); 64 / 80 CUs are too few for the tail (150 / 145 ms), 160 / 192 leave
+    // the compare too little (149 / 182 ms).  (Round 5's 512-thread blocks beside the compares on every CU: the same time at 10^5
+    // plain uniques, 38.3 against 33.9 ms on the deep 10^5 workload, profiles/r09h - removed.)
     {
-      // A sample whose 512-thread blocks would sit on more than half of the CUs: the tail takes HALF of the CUs WHOLE instead
-      // (1024-thread blocks at 128 registers fill a CU's register file) and the compare's kernels have the other half to
-      // themselves at their full occupancy, rather than sharing every CU with a tail block.  10^6 uniques, one box, median of
-      // nine with the XCD-hierarchical barrier: 128 x 1024 135.0-136.5 ms, 245 x 512 136.5-137.4, 96 x 1024 139.3-141.6
-      // (profiles/r08b); with the flat barrier 96 x 1024 led (137.8 vs 144.5 for 245 x 512: r07s, r07t); 64 / 80 CUs are too few
-      // for the tail (150 / 145 ms), 160 / 192 leave the compare too little (149 / 182 ms).
       const int ncu = tail_grid(1 << 30, s->device);
-      if (v3_overlap && K.v3_block == 0 && K.v3_grid == 0 && v3_grid > ncu / 2) {
-        v3_bs = 1024;
-        v3_grid = std::max(1, std::min((N + 8191) / 8192, ncu / 2));
-      }
+      if (v3_overlap && K.v3_grid == 0 && v3_grid > ncu / 2) v3_grid = std::max(1, std::min((N + 8191) / 8192, ncu / 2));
     }
     // (cap: blocks the device can hold at once; 0 = the kernel cannot be resident at all on this part, -1 = the query failed and
     //  the bounded entry barrier is the only guard)
-    if (v3_on) { const int cap = tail_resident_max(s->device, v3_bs); if (cap == 0 || (cap > 0 && v3_grid > cap)) v3_on = false; }
+    if (v3_on) { const int cap = tail_resident_max(s->device); if (cap == 0 || (cap > 0 && v3_grid > cap)) v3_on = false; }
     if (!v3_on) v3_overlap = false;
-    // prefetch screens: the 80-register build where a tail block sits on EVERY CU beside them (three waves per SIMD fit into the
-    // registers the tail leaves, where two of the wide build do); the full build where the tail has taken half of the CUs whole
-    // and the compares have the others to themselves - there the narrow build only spills (29 VGPRs) and moves 1.8x the bytes
-    // (same box, 10^6 uniques: tail 102.7 -> 97.0 ms, pass 143.0 -> 138.7 ms, profiles/r09a_sweep_cfg3_lowreg.jsonl)
-    v3_pf_lowreg = K.v3_pf_lowreg >= 0 ? K.v3_pf_lowreg != 0 : (v3_overlap && v3_bs == 512);
     v3_lock_stride = 0;
     if (v3_on) {
       // uniques one block sweeps: groups of 4096 (ShufLds::U x BS), dealt wave by wave over the blocks (sweep_unique)
@@ -1819,7 +1793,7 @@ struct Run {
     //  for a compare queued behind them holds the device's persistent slot for nothing: configs[3] on one GPU 233 -> 603 ms
     //  when the first sample of each wave happened to start alone, profiles/r08g)
     Ek.pf_plan = (v3_overlap && (active_runs(s->device).load() <= 1 || knobs().v3_overlap == 1)) ? 1 : 0;
-    launch3_tail(Ek, v3_grid, v3_bs, first, (int)(v3_enq + 1), s->h_reads[bi[0].center], stq);
+    launch3_tail(Ek, v3_grid, first, (int)(v3_enq + 1), s->h_reads[bi[0].center], stq);
     ev_end(ev);
     v3_rec.push_back(rec);
     v3_enq++;
@@ -1839,7 +1813,7 @@ struct Run {
     launch2_pf_gate(E2P, (int)k, v3_hflags.p + 32, v3_hflags.p + 40 + (k & 7), st2);
     launch2_pf_tables(E2P, st2);
     int ev = ev_begin(EV_PF_SCREEN, profile_all, false, false, st2);
-    launch2_screen_multi(E2P, st2, /*beside_tail=*/v3_pf_lowreg);
+    launch2_screen_multi(E2P, st2);
     ev_end(ev);
     launch2_batch_lists(E2P, st2);
     const NwBatch nb{&pc->nalign, v3_pf_blistn.p, v3_pf_blist.p, pc->acentre, &pc->abuf, E2.C.Npad, v3_pf_bretry.p, v3_pf_bretryn.p, v2_retrytot.p, &pc->fast_off};
@@ -1888,93 +1862,6 @@ struct Run {
   //  however many are sent)
   bool v3_dev_halted = false;          // the block in the host's hands halted the device: nothing to keep fed until it is answered
 
-  // ---- the replay lane (persistent tail) ---------------------------------------------------------------------------------------
-  // The host's mirror of the partitions (member lists in the reference's order: b_bud's ties, the final clustering) trails the device
-  // through the published moves and births.  That replay is 45-55 ms of a 10^6-unique pass and used to run between the waits of
-  // the thread that also feeds the device: a persistent launch that left (a compare due) found nobody to send the next one until
-  // the block in hand was replayed - with ONE launch in flight that is device time.  A block that asks nothing of the host (birth
-  // applied on the device, movers inline) is now copied out of the ring and handed to a second host thread, which replays it,
-  // re-derives the decision from the published candidates (decide_bud: must equal the device's) and books the birth, in block
-  // order; the boundary thread drains the lane before it touches the mirror itself (a halt that wants the host's decision, a
-  // paused block, the end of the rounds).  Off when the caller wants the verbose log (its callback runs on the calling thread).
-  struct ReplayLane {
-    std::thread th;
-    std::mutex mu;                                       // guards q and err
-    std::deque<std::unique_ptr<unsigned char[]>> q;
-    std::atomic<long> pushed{0}, done{0};                // blocks handed over / worked through (the lane polls: a futex wake per
-    std::atomic<bool> stop{false};                       //  block on the thread that feeds the device cost 2-3 ms of a pass)
-    std::exception_ptr err;
-    std::thread::id tid;
-  } lane;
-  bool lane_on = false;
-  bool lane_is_me() const { return lane_on && std::this_thread::get_id() == lane.tid; }
-  void lane_start() {
-    lane.stop.store(false); lane.pushed.store(0); lane.done.store(0); lane.err = nullptr;
-    const bool polite = wait_blocks();
-    std::unique_lock<std::mutex> hold(lane.mu);                    // (the thread's first look at the queue waits until tid is written)
-    lane.th = std::thread([this, polite]() {
-      (void)hipSetDevice(s->device);
-      for (unsigned idle = 0;;) {
-        if (lane.done.load(std::memory_order_relaxed) == lane.pushed.load(std::memory_order_acquire)) {
-          if (lane.stop.load(std::memory_order_acquire)) return;
-          cpu_relax();
-          if (polite || ++idle > 200000u) { struct timespec ts{0, 20000}; nanosleep(&ts, nullptr); }   // (a lane nobody feeds stops burning its core)
-          continue;
-        }
-        idle = 0;
-        std::unique_ptr<unsigned char[]> job;
-        bool failed;
-        {
-          std::lock_guard<std::mutex> lk(lane.mu);
-          job = std::move(lane.q.front());
-          lane.q.pop_front();
-          failed = (bool)lane.err;
-        }
-        try {
-          if (!failed) {
-            const Round2Out &b = *(const Round2Out *)job.get();
-            v2_replay(b, 0);
-            Birth bb = decide_bud(b.bud);
-            if (!bb.yes || bb.type != 'A' || bb.c.raw != b.bud.ties[0][0].raw)
-              throw RuntimeErr{DADA2HIP_ERR_RUNTIME, "dada2hip: internal error: device and host bud decisions differ"};
-            record_birth(bb);
-          }
-        } catch (...) {
-          std::lock_guard<std::mutex> lk(lane.mu);
-          if (!lane.err) lane.err = std::current_exception();
-        }
-        lane.done.fetch_add(1, std::memory_order_release);
-      }
-    });
-    lane.tid = lane.th.get_id();
-    lane_on = true;
-  }
-  // a block the host has nothing to answer: its used part copied out of the ring (header, candidates, inline movers)
-  void lane_push(const Round2Out &b, int tot) {
-    const size_t bytes = offsetof(Round2Out, mov) + (size_t)3 * (size_t)tot * 4;
-    std::unique_ptr<unsigned char[]> job(new unsigned char[(bytes + 15) & ~(size_t)15]);
-    memcpy(job.get(), &b, bytes);
-    {
-      std::lock_guard<std::mutex> lk(lane.mu);
-      lane.q.push_back(std::move(job));
-    }
-    lane.pushed.fetch_add(1, std::memory_order_release);
-  }
-  // everything handed over has been replayed (its exception, if it raised one, surfaces here)
-  void lane_drain() {
-    if (!lane_on) return;
-    while (lane.done.load(std::memory_order_acquire) != lane.pushed.load(std::memory_order_relaxed)) cpu_relax();
-    std::lock_guard<std::mutex> lk(lane.mu);
-    if (lane.err) { std::exception_ptr e = lane.err; lane.err = nullptr; std::rethrow_exception(e); }
-  }
-  bool lane_failed() { std::lock_guard<std::mutex> lk(lane.mu); return (bool)lane.err; }
-  void lane_stop() noexcept {
-    if (!lane.th.joinable()) { lane_on = false; return; }
-    lane.stop.store(true, std::memory_order_release);
-    lane.th.join();                                      // (it works through what is queued first: nothing it touches goes away before)
-    { std::lock_guard<std::mutex> lk(lane.mu); lane.q.clear(); }
-    lane_on = false;
-  }
   void v3_topup() {
     if (v3_dev_halted) return;
     const long need = (long)v3_depth - (v3_enq - v3_ended());
@@ -2023,14 +1910,15 @@ struct Run {
   }
 
   // run_dada's loop (Rmain.cpp:312-331) with the rounds inside persistent launches: the host keeps v2_depth super-chains queued,
-  // trails the device through the published result blocks exactly as with the launch chains, and answers the same halts
+  // trails the device through the published result blocks exactly as with the launch chains, and answers the same halts.
+  // (The replay runs on this thread: handing it to a second host thread read 127.4-130 against 123.7-125.4 ms per 10^6-unique
+  //  pass while the device is the bound, profiles/r10c - removed.)
   void run_v3(int max_clust) {
     // the device's persistent slot is held for the rounds only.  An exception (abort hook, time-out, internal error) can leave
     // launches of this run queued or running: they are halted and waited for BEFORE the slot goes to the next run, which would
     // otherwise put its own persistent kernel beside a dying one
-    struct SlotGuard { Run *r; ~SlotGuard() { r->lane_stop(); if (r->v3_running) r->v3_quiesce(); r->v3_release(); r->v3_running = false; } } slot_guard{this};
+    struct SlotGuard { Run *r; ~SlotGuard() { if (r->v3_running) r->v3_quiesce(); r->v3_release(); r->v3_running = false; } } slot_guard{this};
     v3_running = true;
-    if (knobs().v3_lane != 0 && !(o.verbose && hooks && hooks->log) && !v2_debug) lane_start();
     auto t0 = clk::now();
     st.nstored = (uint64_t)N;                                  // round 0 keeps every comparison (E_minmax starts at -999)
     v3_rec.clear();
@@ -2052,8 +1940,6 @@ struct Run {
       catch (const TailEntryFailed &) {
         // every queued launch has ended and none of them has touched the state since the last consumed block: hand the rounds
         // to the launch chains from exactly here
-        lane_drain();                                          // (the mirror is the boundary thread's again)
-        lane_stop();
         v3_running = false;
         v3_fallback();
         st.ms_bookkeep += ms_since(t0);
@@ -2070,13 +1956,7 @@ struct Run {
                 b.kord, b.halt, b.paused, b.nclust, b.nsh, b.cnt[0], b.cnt[1], b.cnt[2], b.cnt[3], b.nbatch, b.slot, b.birth_applied, b.bud.found[0],
                 b.bud.nties[0], b.bud.best_p[0], b.blk_count);
       v3_dev_halted = b.halt != H2_NONE;                       // (a paused block is resumed inside v2_replay, before its moves are replayed)
-      int tot_mov = 0;
-      for (int l = 0; l < b.nsh; l++) tot_mov += b.cnt[l];
-      // the replay lane takes the block when the host has nothing to answer (the lane raises what the block's flags or its
-      // decision would have raised here; a lane that has failed hands everything back so that the error surfaces at once)
-      const bool to_lane = lane_on && b.halt == H2_NONE && b.paused == 0 && tot_mov <= E2.mov_inline && b.birth_applied != 0 && !lane_failed();
-      if (to_lane) lane_push(b, tot_mov);
-      else { lane_drain(); v2_replay(b, seq, /*resume_after_fetch=*/b.paused != 0 && b.halt == H2_NONE); }
+      v2_replay(b, seq, /*resume_after_fetch=*/b.paused != 0 && b.halt == H2_NONE);
       n_halt[b.halt & 7]++;
       if (b.kord > v3_ord_seen) {                              // first block of its launch: the compare in front of that launch served it
         v3_ord_seen = b.kord;
@@ -2092,11 +1972,6 @@ struct Run {
       }
       switch (b.halt) {
         case H2_NONE: {                                        // birth applied on the device: book it
-          if (to_lane) {                                       // (the lane books it behind the block's moves)
-            nclust_dev = b.nclust;
-            st.ncompare += (uint64_t)N;
-            break;
-          }
           Birth bb = decide_bud(b.bud);
           if (!bb.yes || bb.type != 'A' || bb.c.raw != b.bud.ties[0][0].raw)
             throw RuntimeErr{DADA2HIP_ERR_RUNTIME, "dada2hip: internal error: device and host bud decisions differ"};
@@ -2135,8 +2010,6 @@ struct Run {
       v3_dev_halted = false;                                   // (answered: host birth / resume are in the stream)
       *(volatile int32_t *)v3_hflags.p = (int32_t)v2_cons;     // the device may reuse the ring slots of everything consumed
     }
-    lane_drain();
-    lane_stop();
     v3_running = false;
     sync_spin(s->stream);                                      // launches queued behind the final halt
     if (v3_overlap) {
@@ -2162,10 +2035,10 @@ struct Run {
     }
     st.tail_xcd_barrier = (E2.xbar && v3_grid > 1) ? 1u : 0u;
     st.tail_mirror = (v3_enq > 0 && E2.mirror_on) ? 1u : 0u;
-    st.tail_launches = (uint64_t)v3_enq; st.tail_pauses = (uint64_t)n_pause; st.tail_blocks = (uint32_t)v3_grid; st.tail_threads = (uint32_t)v3_bs;
+    st.tail_launches = (uint64_t)v3_enq; st.tail_pauses = (uint64_t)n_pause; st.tail_blocks = (uint32_t)v3_grid; st.tail_threads = 1024;
     if (knobs().v2_summary && v3_overlap)
-      fprintf(stderr, "[v3] overlap: prefetch compares %ld in %ld chains (centres %d)  rounds served from a prefetched batch %d  waits inside the launch %d  launches left for one %d  threads per block %d\n",
-              v3_pf_seen, v3_pf_chains, v3_pf_stat[3], v3_pf_stat[0], v3_pf_stat[1], v3_pf_stat[2], v3_bs);
+      fprintf(stderr, "[v3] overlap: prefetch compares %ld in %ld chains (centres %d)  rounds served from a prefetched batch %d  waits inside the launch %d  launches left for one %d\n",
+              v3_pf_seen, v3_pf_chains, v3_pf_stat[3], v3_pf_stat[0], v3_pf_stat[1], v3_pf_stat[2]);
     if (knobs().v2_summary)
       fprintf(stderr, "[v3] blocks %ld  launches %ld  grid %d  halts none/nobirth/host/more/cap/max %ld %ld %ld %ld %ld %ld  pauses %ld  ms: wait %.1f replay %.1f enqueue %.1f total %.1f  moves %llu misses %llu\n",
               n_blocks, v3_enq, v3_grid, n_halt[0], n_halt[1], n_halt[2], n_halt[3], n_halt[4], n_halt[5], n_pause, st.ms_wait_device, st.ms_replay,
@@ -2174,52 +2047,20 @@ struct Run {
   }
 
   // one chain: [shuffle x nlev][b_p_update + b_bud arg-min + ties][birth / plan / publish]; a full round is a chain with the
-  // batch compare in front (no-ops on a cache hit) and the round's store filter in its first shuffle
-  // A full round is always the same launches with the same arguments (what differs lives in the control block), so it can be
-  // captured once into a hipGraph and replayed: one API call per round (DADA2HIP_V2_GRAPH=1; off by default, see graph_off()),
-  // ... in both forms: [0] with the batch compare in front, [1] without (Eng2::has_compare)
-  hipGraphExec_t v2_graph[2] = {nullptr, nullptr};
-  int v2_graph_state = 0;            // 0: not tried yet, 1: in use, -1: unavailable
+  // batch compare in front (no-ops on a cache hit) and the round's store filter in its first shuffle.
+  // (Always plain launches: replaying a round captured into a hipGraph left a 13 us bubble behind its last kernel, 183 against
+  //  173 ms per pass at 10^6 uniques, profiles/r03x vs r03w - removed.)
   int v2_plain_rounds = 0;
   long v2_next_full = 0;             // first chain (sequence number) that is expected to need a batch compare again
   bool v2_lite_on = true;
   bool v2_align_commit = false;       // Eng2::align_at_commit
-  void v2_drop_graph() {
-    for (auto &g : v2_graph) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-    if (v2_graph_state == 1) v2_graph_state = 0;
-  }
-  bool v2_try_graph() {
-    if (graph_off() || profile_all || v2_graph_state < 0) return false;
-    if (v2_graph_state == 1) return true;
-    if (v2_plain_rounds < 1) return false;   // the first round goes out plainly (one-time function attributes are set by its launches)
-    hipStream_t stq = s->stream;
-    for (int lite = 0; lite < 2; lite++) {
-      hipGraph_t g = nullptr;
-      if (hipStreamBeginCapture(stq, hipStreamCaptureModeRelaxed) != hipSuccess) { (void)hipGetLastError(); v2_drop_graph(); v2_graph_state = -1; return false; }
-      v2_round_launches(v2_chain, true, true, nullptr, lite != 0);
-      if (hipStreamEndCapture(stq, &g) != hipSuccess || !g) { (void)hipGetLastError(); v2_drop_graph(); v2_graph_state = -1; return false; }
-      const hipError_t e = hipGraphInstantiate(&v2_graph[lite], g, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(g);
-      if (e != hipSuccess) { (void)hipGetLastError(); v2_graph[lite] = nullptr; v2_drop_graph(); v2_graph_state = -1; return false; }
-    }
-    v2_graph_state = 1;
-    return true;
-  }
-  // hipGraph replay is OFF by default: a graph launch leaves a 13 us bubble behind its last kernel (profiles/r03h, r03s), 10 ms
-  // per pass at 10^6 uniques, while the six or ten plain launches of a chain cost the host 25 us per round - a third of what
-  // it has (it trails the device anyway) - and run back to back: 173 against 183 ms per pass (profiles/r03x vs r03w).
-  // DADA2HIP_V2_GRAPH=1 brings the graphs back (a host that is short of cycles: 8 instead of 25 ms of enqueue per pass).
-  static bool graph_off() { return !knobs().v2_graph; }
   void v2_enqueue_chain(int nlev, bool with_compare, bool store) {
     const auto t_enq = clk::now();
     EnqRec rec{-1, -1, with_compare};
     // a round that is expected to find its centre cached goes out without the batch compare's launches (engine.h, Eng2::has_compare)
     const bool lite = with_compare && v2_lite_on && v2_plain_rounds >= 1 && v2_enq + 1 < v2_next_full;
-    if (nlev == v2_chain && with_compare && store && v2_try_graph()) D2_HIP(hipGraphLaunch(v2_graph[lite ? 1 : 0], s->stream));
-    else {
-      v2_round_launches(nlev, with_compare, store, &rec, lite);
-      if (with_compare) v2_plain_rounds++;
-    }
+    v2_round_launches(nlev, with_compare, store, &rec, lite);
+    if (with_compare) v2_plain_rounds++;
     if (lite) st.lite_chains++;   // (sending the chains behind an expected refill without a compare as well was tried: as many
                                   //  more wrong guesses as it saved launches, profiles/README.md r03u)
     v2_enqrec.push_back(rec);
@@ -2623,7 +2464,7 @@ void sample_run(dada2hip_sample *s, const double *err, int err_ncol, const dada2
   // alignments per wave
   const int fk = knobs().nw_kernel;
   const bool coop_fin_ok = opts->band_size != 0 && nw_ad_lds_bytes(D, run.ap) > 0 && nw_ad_lds_bytes(D, run.ap) <= 150 * 1024;
-  bool coop_fin = coop_fin_ok && N < COOP_MAX_BATCH;
+  bool coop_fin = coop_fin_ok && N < COOP_BATCH_LIMIT;
   if (fk == NWK_LANE) coop_fin = false;
   if (fk == NWK_COOP && coop_fin_ok) coop_fin = true;
   // band windows too wide for the LDS-pointer kernel: the wide anti-diagonal kernel (same rule as compare_round)

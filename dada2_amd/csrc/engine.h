@@ -524,7 +524,7 @@ enum { KT_S0 = 0, KT_S0_BAR, KT_SL, KT_SL_BAR, KT_P, KT_P_BAR, KT_BIRTH, KT_PUBL
 
 void launch2_store0(const Eng2 &E, const double *d_lam, const uint32_t *d_ham, const uint8_t *d_cls, const int32_t *d_round_counters,
                     hipStream_t st);
-void launch2_screen_multi(const Eng2 &E, hipStream_t st, bool beside_tail = false);   // beside_tail: the 80-register build (prefetch compares)
+void launch2_screen_multi(const Eng2 &E, hipStream_t st);
 // prefetch compare (second stream): the k-mer tables of the batch pf_ctl describes (the planner only chose its centres) in front
 // of the screen, the completion word behind the aligner.  E = the prefetch's argument block (see Eng2::pf_on)
 void launch2_pf_gate(const Eng2 &E, int k, const int32_t *h_quit, int32_t *h_result, hipStream_t st);   // first kernel of chain k: waits for plan k (pinned quit / result words)
@@ -541,9 +541,9 @@ void launch2_posthoc(const Eng2 &E, const int32_t *d_cluster_of_centre, int32_t 
 // the persistent round tail: rounds run back to back inside ONE launch of `grid` co-resident blocks until a compare is due, the
 // device halts or the host's ring fills up.  first: the evaluation behind round 0 (no shuffle).  ordinal: this launch's number.
 int tail_grid(int N, int device);
-int tail_resident_max(int device, int bs);                  // blocks of k3_tail the device can hold at once (occupancy query; 0 = unknown)
-int tail_mirror_cap(int device, int bs);                    // uniques per block the tail's LDS mirror holds (Eng2::mirror_on; 0: its LDS does not fit this part)
-void launch3_tail(const Eng2 &E, int grid, int bs, bool first, int ordinal, uint32_t init_reads, hipStream_t st);   // bs: 1024 or 512 threads per block
+int tail_resident_max(int device);                          // blocks of k3_tail the device can hold at once (occupancy query; 0 = unknown)
+int tail_mirror_cap(int device);                            // uniques per block the tail's LDS mirror holds (Eng2::mirror_on; 0: its LDS does not fit this part)
+void launch3_tail(const Eng2 &E, int grid, bool first, int ordinal, uint32_t init_reads, hipStream_t st);   // 1024 threads per block
 
 // get_lr + get_ham_endsfree (chimera.cpp:211-293) on the move strings k_nw left behind: out[slot] = {left, right, left_oo, right_oo, ham}
 void launch_bimera_lr(const SampleDev &S, const int32_t *d_chunk_centre, const int32_t *d_work, int nwork, const uint8_t *d_moves,

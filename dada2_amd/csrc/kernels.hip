@@ -250,8 +250,8 @@ void launch_screen(const SampleDev &S, int centre, const ScreenParams &sp, const
                    int32_t *d_gl_list, int32_t *d_counters, uint32_t *d_ctab, bool build_table, const int32_t *d_centre_dev,
                    hipStream_t st) {
   if (build_table) hipLaunchKernelGGL(k_centre_table, dim3(1), dim3(256), 0, st, S, centre, d_ctab);
-  const int grid_cap = std::max(1, knobs().screen_grid);
-  int grid = std::min((S.N + 15) / 16, grid_cap);
+  constexpr int K_SCREEN_MAX_BLOCKS = 2048;   // blocks of k_screen
+  int grid = std::min((S.N + 15) / 16, K_SCREEN_MAX_BLOCKS);
   int iters = ((S.N + 15) / 16 + grid - 1) / grid;
   int cap = iters * 16;
   size_t lds = (size_t)(CTAB_ORD + 8) * 4 + (size_t)cap * 8 + (size_t)S.LK * 2 + 32;

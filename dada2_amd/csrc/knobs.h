@@ -4,6 +4,7 @@
 // (knobs_reload(), called by the C-ABI entry points); everything below the boundary reads `knobs()`.  Nothing else in the
 // library calls getenv.  The supported set is listed in include/dada2hip.h ("Environment"); all default to "off" / automatic,
 // and none changes a result - they choose engines, kernel families and buffer sizes, which the parity tests sweep.
+// The variables read are exactly the ones named beside the fields of Knobs below (DESIGN.md has the same list as a table).
 #pragma once
 #include <atomic>
 #include <cstdlib>
@@ -27,7 +28,6 @@ struct Knobs {
   int v2_nbuf = 0;                    // DADA2HIP_V2_NBUF               cached batch buffers (0 = automatic: <= 64, <= 1/8 of the device)
   int v2_depth = 0;                   // DADA2HIP_V2_DEPTH              rounds / super-chains enqueued ahead (0 = automatic: 2)
   int v2_chain = 0;                   // DADA2HIP_V2_CHAIN              shuffle calls per launch chain (0 = automatic: 4)
-  bool v2_graph = false;              // DADA2HIP_V2_GRAPH=1            hipGraph replay of the launch chains
   int v2_lite = -1;                   // DADA2HIP_V2_LITE=0|1           chains expected to hit the cache go out without the compare launches
   int v2_align = -1;                  // DADA2HIP_V2_ALIGN=commit|batch when the pairs of a batch are aligned (1 / 0; -1 = automatic)
   int v2_filter = -1;                 // DADA2HIP_V2_FILTER=0|1         later shuffle calls visit only the uniques the previous call can have unsettled
@@ -37,7 +37,6 @@ struct Knobs {
   bool v2_tail_chain = false;         // DADA2HIP_V2_TAIL=chain         the round tail as launch chains instead of the persistent kernel
   int v3_grid = 0;                    // DADA2HIP_V3_GRID               blocks of the persistent launch (tests: several blocks on a small sample)
   int v3_ring = 0;                    // DADA2HIP_V3_RING               result blocks the device may be ahead of the host (tests: a host that lags)
-  int v3_block = 0;                   // DADA2HIP_V3_BLOCK=512|1024     threads per block of the persistent tail (0 = automatic)
   int v3_overlap = -1;                // DADA2HIP_V3_OVERLAP=0|1        the next batch's compare under the persistent tail, on a second stream (-1 = automatic)
   int v3_pf_wait_us = -1;             // DADA2HIP_V3_PF_WAIT_US         how long the tail spins for a prefetched compare before it leaves the launch
   int v3_pf_early = -1;               // DADA2HIP_V3_PF_EARLY=n         (tuning) plan the next prefetch n positions into the batch before the newest (0-8)
@@ -46,10 +45,8 @@ struct Knobs {
   int v3_spec = 1;                     // DADA2HIP_V3_SPEC=0|1           the round's evaluation rides on its shuffle calls (0: a phase of its own behind them, round 4's form)
   int v3_spec_max = -1;               // DADA2HIP_V3_SPEC_MAX=n         (tuning) ... only behind a call that moved at most n uniques
   int v3_pf_sync = 0;                 // DADA2HIP_V3_PF_SYNC=1          (measurement) every prefetch is waited for at the next serial end, the tail resident and idle
-  int v3_pf_lowreg = -1;              // DADA2HIP_V3_PF_LOWREG=0|1      (tuning) prefetch screens on the 80-register build of the screen kernel (-1 = automatic: where the tail shares every CU)
   int replay_radix_min = 4096;        // DADA2HIP_REPLAY_RADIX_MIN=n    test knob: mover lists from n entries on are ordered by the radix sort of the host's replay (1 = always)
   int v3_slots = 3;                   // DADA2HIP_V3_SLOTS=n            persistent launches of this process side by side on one device (several samples in flight; 1 = their rounds take turns)
-  int v3_lane = 0;                    // DADA2HIP_V3_LANE=1             the host's replay of moves and births on a second host thread (run_v3's replay lane; measured 3-4 ms SLOWER per 10^6-unique pass while the device is the bound: not the default)
   int v3_mirror = 1;                  // DADA2HIP_V3_MIRROR=0           the persistent tail reads every unique's partition / flags from global memory in each sweep (no LDS mirror)
   int v3_fail_entry = 0;              // DADA2HIP_V3_FAIL_ENTRY=n       test knob: the n-th persistent launch fails its entry barrier (-> launch chains)
   bool v2_debug = false;              // DADA2HIP_V2_DEBUG              per-block trace on stderr
@@ -62,9 +59,6 @@ struct Knobs {
   long long node_cap = 0;             // DADA2HIP_NODE_CAP              first allocation of the comparison store (tests: the growth path)
   bool wait_block = false;            // DADA2HIP_WAIT=block            blocking synchronisation instead of spinning
   double wait_timeout_s = 600.0;      // DADA2HIP_WAIT_TIMEOUT_S        bound on every host-side device wait
-  int coop_max = 4000000;             // DADA2HIP_COOP_MAX              (experiment) uniques above which round 0 leaves k_nw_ad
-  bool kord_align = false;            // DADA2HIP_KORD_ALIGN=1          (experiment) k-mer rows padded to 64 bytes
-  int screen_grid = 2048;             // DADA2HIP_SCREEN_GRID           (experiment) block cap of k_screen
   long long ad_fcap = 0;              // DADA2HIP_AD_FCAP               rows of k_ad_product's offset buffer (tests: the in-kernel product)
   int screen_bits = 1;                // DADA2HIP_SCREEN_BITS=0         no 5-mer presence bitmaps: the batch screen walks every unique's k-mer record
   int ad_fast = 1;                    // DADA2HIP_AD_FAST=0             batch compares on the full aligner only (no pointer-free first pass)
@@ -77,10 +71,17 @@ struct Knobs {
   int host_threads = 0;
   int alloc_cache = -1;
   long long alloc_cache_gb = -1;
+  // what the environment said: "NAME=text" of every variable from_env looked up and found set, in lookup order.  Two snapshots
+  // are the same settings exactly when these strings are equal (knobs_reload) - nothing to keep in step when a knob is added.
+  std::string env_text;
 
   static Knobs from_env() {
     Knobs k;
-    auto S = [](const char *n) -> const char * { return std::getenv(n); };
+    auto S = [&k](const char *n) -> const char * {   // every lookup goes through here, and leaves its text in env_text
+      const char *e = std::getenv(n);
+      if (e) k.env_text.append(n).append(1, '=').append(e).append(1, '\n');
+      return e;
+    };
     auto I = [&](const char *n, int dflt) -> int { const char *e = S(n); return e ? std::atoi(e) : dflt; };
     auto B = [&](const char *n) -> bool { const char *e = S(n); return e && std::atoi(e) != 0; };
     auto T = [&](const char *n) -> int { const char *e = S(n); return e ? (std::atoi(e) != 0 ? 1 : 0) : -1; };   // tri-state
@@ -90,19 +91,17 @@ struct Knobs {
     k.no_speculation = S("DADA2HIP_NO_SPECULATION") != nullptr;
     k.no_autobirth = S("DADA2HIP_NO_AUTOBIRTH") != nullptr;
     k.v2_nbuf = I("DADA2HIP_V2_NBUF", 0); k.v2_depth = I("DADA2HIP_V2_DEPTH", 0); k.v2_chain = I("DADA2HIP_V2_CHAIN", 0);
-    k.v2_graph = B("DADA2HIP_V2_GRAPH");
     k.v2_lite = T("DADA2HIP_V2_LITE");
     if (const char *e = S("DADA2HIP_V2_ALIGN")) k.v2_align = !std::strcmp(e, "commit") ? 1 : 0;
     k.v2_filter = T("DADA2HIP_V2_FILTER");
     k.v2_grid_shuffle = I("DADA2HIP_V2_GRID_SHUFFLE", 0); k.v2_grid_pupdate = I("DADA2HIP_V2_GRID_PUPDATE", 0);
     k.v2_mov_inline = I("DADA2HIP_V2_MOV_INLINE", 0);
     if (const char *e = S("DADA2HIP_V2_TAIL")) k.v2_tail_chain = !std::strcmp(e, "chain");
-    k.v3_grid = I("DADA2HIP_V3_GRID", 0); k.v3_ring = I("DADA2HIP_V3_RING", 0); k.v3_block = I("DADA2HIP_V3_BLOCK", 0);
+    k.v3_grid = I("DADA2HIP_V3_GRID", 0); k.v3_ring = I("DADA2HIP_V3_RING", 0);
     k.v3_overlap = T("DADA2HIP_V3_OVERLAP"); k.v3_pf_wait_us = I("DADA2HIP_V3_PF_WAIT_US", -1);
     k.v3_fail_entry = I("DADA2HIP_V3_FAIL_ENTRY", 0); k.v3_spec = I("DADA2HIP_V3_SPEC", 1); k.v3_xbar = T("DADA2HIP_V3_XBAR"); k.v3_spec_max = I("DADA2HIP_V3_SPEC_MAX", -1);
-    k.v3_pf_early = I("DADA2HIP_V3_PF_EARLY", -1); k.v3_pf_lowreg = T("DADA2HIP_V3_PF_LOWREG"); k.v3_pf_sync = I("DADA2HIP_V3_PF_SYNC", 0); k.v3_pf_gate_us = I("DADA2HIP_V3_PF_GATE_US", -1);
+    k.v3_pf_early = I("DADA2HIP_V3_PF_EARLY", -1); k.v3_pf_sync = I("DADA2HIP_V3_PF_SYNC", 0); k.v3_pf_gate_us = I("DADA2HIP_V3_PF_GATE_US", -1);
     k.v3_mirror = I("DADA2HIP_V3_MIRROR", 1);
-    k.v3_lane = I("DADA2HIP_V3_LANE", 0);
     k.v3_slots = I("DADA2HIP_V3_SLOTS", 3);
     k.replay_radix_min = I("DADA2HIP_REPLAY_RADIX_MIN", 4096);
     k.v2_debug = S("DADA2HIP_V2_DEBUG") != nullptr; k.v2_summary = S("DADA2HIP_V2_SUMMARY") != nullptr;
@@ -115,9 +114,6 @@ struct Knobs {
     if (const char *e = S("DADA2HIP_NODE_CAP")) k.node_cap = std::atoll(e);
     if (const char *e = S("DADA2HIP_WAIT")) k.wait_block = !std::strcmp(e, "block");
     if (const char *e = S("DADA2HIP_WAIT_TIMEOUT_S")) k.wait_timeout_s = std::atof(e);
-    k.coop_max = I("DADA2HIP_COOP_MAX", 4000000);
-    if (const char *e = S("DADA2HIP_KORD_ALIGN")) k.kord_align = !std::strcmp(e, "1");
-    k.screen_grid = I("DADA2HIP_SCREEN_GRID", 2048);
     if (const char *e = S("DADA2HIP_AD_FCAP")) k.ad_fcap = std::atoll(e);
     k.ad_debug = I("DADA2HIP_AD_DEBUG", 0); k.ad_fast = I("DADA2HIP_AD_FAST", 1); k.screen_bits = I("DADA2HIP_SCREEN_BITS", 1);
     if (const char *e = S("DADA2HIP_BIMERA_TIMES")) k.bimera_times = !std::strcmp(e, "1");
@@ -133,19 +129,6 @@ struct Knobs {
 namespace knobs_detail {
 inline std::mutex &mu() { static std::mutex m; return m; }          // serialises reloads only
 inline std::atomic<const Knobs *> &cur() { static std::atomic<const Knobs *> p{nullptr}; return p; }
-inline bool same(const Knobs &a, const Knobs &b) {
-  // (field-wise: the struct holds a std::string)
-  return a.engine_classic == b.engine_classic && a.nw_kernel == b.nw_kernel && a.ad_homo == b.ad_homo && a.no_speculation == b.no_speculation &&
-         a.no_autobirth == b.no_autobirth && a.v2_nbuf == b.v2_nbuf && a.v2_depth == b.v2_depth && a.v2_chain == b.v2_chain && a.v2_graph == b.v2_graph &&
-         a.v2_lite == b.v2_lite && a.v2_align == b.v2_align && a.v2_filter == b.v2_filter && a.v2_grid_shuffle == b.v2_grid_shuffle &&
-         a.v2_grid_pupdate == b.v2_grid_pupdate && a.v2_mov_inline == b.v2_mov_inline && a.v2_tail_chain == b.v2_tail_chain && a.v3_grid == b.v3_grid &&
-         a.v3_ring == b.v3_ring && a.v3_block == b.v3_block && a.v3_overlap == b.v3_overlap && a.v3_pf_wait_us == b.v3_pf_wait_us &&
-         a.v3_fail_entry == b.v3_fail_entry && a.v3_spec == b.v3_spec && a.v3_xbar == b.v3_xbar && a.v3_spec_max == b.v3_spec_max && a.v3_pf_early == b.v3_pf_early && a.v3_pf_lowreg == b.v3_pf_lowreg && a.v3_pf_sync == b.v3_pf_sync && a.v3_pf_gate_us == b.v3_pf_gate_us && a.v3_mirror == b.v3_mirror && a.v3_lane == b.v3_lane && a.v3_slots == b.v3_slots && a.replay_radix_min == b.replay_radix_min && a.v2_debug == b.v2_debug && a.v2_summary == b.v2_summary && a.v2_trace_on == b.v2_trace_on &&
-         a.v2_trace_seq == b.v2_trace_seq && a.v2_trace_file == b.v2_trace_file && a.profile == b.profile && a.node_cap == b.node_cap &&
-         a.wait_block == b.wait_block && a.wait_timeout_s == b.wait_timeout_s && a.coop_max == b.coop_max && a.kord_align == b.kord_align &&
-         a.screen_grid == b.screen_grid && a.ad_fcap == b.ad_fcap && a.ad_debug == b.ad_debug && a.ad_fast == b.ad_fast && a.screen_bits == b.screen_bits && a.bimera_times == b.bimera_times && a.derep_times == b.derep_times && a.derep_zlib == b.derep_zlib &&
-         a.host_threads == b.host_threads && a.alloc_cache == b.alloc_cache && a.alloc_cache_gb == b.alloc_cache_gb;
-}
 }  // namespace knobs_detail
 
 // Re-read the environment (every C-ABI entry point does, once, before anything else).  A snapshot that differs from the current
@@ -163,7 +146,7 @@ inline void knobs_reload() {
   Knobs k = Knobs::from_env();
   std::lock_guard<std::mutex> g(knobs_detail::mu());
   const Knobs *c = knobs_detail::cur().load(std::memory_order_relaxed);
-  if (!c || !knobs_detail::same(*c, k)) knobs_detail::cur().store(new Knobs(std::move(k)), std::memory_order_release);
+  if (!c || c->env_text != k.env_text) knobs_detail::cur().store(new Knobs(std::move(k)), std::memory_order_release);
 }
 // (an acquire load: knobs() is called from polling loops and per-round paths of several host threads - no lock on the read side)
 inline const Knobs &knobs() {

@@ -1685,10 +1685,9 @@ __global__ void k2_pf_done(Eng2 E) {
 // when (and if) a centre's round comes.
 struct ScrIn { uint4 c0, c1; int Lr, nh; uint32_t rd; bool lk; };
 
-// CORES: waves per SIMD the kernel is compiled for.  4 (123 registers) when it has the device to itself; 6 (80 registers, a few
-// spilled) for the prefetch compares that run BESIDE the persistent tail, which holds half of every CU's registers: the screen's
-// throughput is its resident blocks (every block waits for its rows most of the time), and three waves per SIMD fit into the
-// other half where two of the wide build do (profiles/r07c: 485 us beside the tail against 246 us alone).
+// WAVES: waves per SIMD the kernel is compiled for.  4 (123 registers) is the one build.  (A 6-wave, 80-register build served the
+// prefetch compares while they ran BESIDE a 512-thread tail on every CU; with the tail on CUs of its own it only spilled - 10^6
+// uniques: pass 143.0 -> 138.7 ms on the wide build, profiles/r09a_sweep_cfg3_lowreg.jsonl - and went with that tail.)
 template <int WAVES>
 __global__ __launch_bounds__(256, WAVES) void k2_screen_multi(Eng2 E) {
   const Ctl2 *ctl = E.ctl;
@@ -1967,19 +1966,17 @@ void launch2_pf_gate(const Eng2 &E, int k, const int32_t *h_quit, int32_t *h_res
 }
 void launch2_pf_tables(const Eng2 &E, hipStream_t st) { hipLaunchKernelGGL(k2_pf_tables, dim3(1), dim3(1024), 0, st, E); }
 void launch2_pf_done(const Eng2 &E, hipStream_t st) { hipLaunchKernelGGL(k2_pf_done, dim3(1), dim3(64), 0, st, E); }
-void launch2_screen_multi(const Eng2 &E, hipStream_t st, bool beside_tail) {
+void launch2_screen_multi(const Eng2 &E, hipStream_t st) {
   const size_t lds = (size_t)NKMER * 8 + (size_t)KB_MAX * E.S.LK * 2 + (size_t)(E.S.maxlen + 2) * 4 + 16;
   static size_t attr_set[64] = {0};
   int dev_ = 0;
   (void)hipGetDevice(&dev_);
   if (lds > attr_set[dev_ & 63]) {
     (void)hipFuncSetAttribute((const void *)k2_screen_multi<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void *)k2_screen_multi<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set[dev_ & 63] = lds;
   }
   const int grid = std::min((E.S.N + 63) / 64, 2048);
-  if (beside_tail) hipLaunchKernelGGL(k2_screen_multi<6>, dim3(grid), dim3(256), lds, st, E);
-  else hipLaunchKernelGGL(k2_screen_multi<4>, dim3(grid), dim3(256), lds, st, E);
+  hipLaunchKernelGGL(k2_screen_multi<4>, dim3(grid), dim3(256), lds, st, E);
 }
 void launch2_shuffle(const Eng2 &E, int level, bool store, hipStream_t st) {
   const int grid = std::min((E.S.N + 255) / 256, (int)E.grid_shuffle);   // one device atomic per counter per block

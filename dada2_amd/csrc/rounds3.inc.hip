@@ -362,15 +362,18 @@ __global__ __launch_bounds__(BS, BS == 512 ? 2 : 4) void k3_tail(Eng2 E, BudKey 
 }
 
 // Per-device facts of the persistent tail, established ONCE per device and process (std::call_once: dada2hip_run_multi's host threads
-// come through here side by side): the CU count, the dynamic-LDS attribute of both instances, and how many blocks of each the
-// device can hold at once.  cap: > 0 blocks, 0 = the kernel cannot be resident at all (its LDS does not fit this part, or the
+// come through here side by side): the CU count, the kernel's dynamic-LDS attribute, and how many of its blocks the device can
+// hold at once.  cap: > 0 blocks, 0 = the kernel cannot be resident at all (its LDS does not fit this part, or the
 // attribute was refused: the run then goes to the launch chains instead of failing at its first launch), -1 = the query failed
 // (unknown: the bounded entry barrier is what stands between a grid that cannot be co-resident and a hang).
+// (One instance, 1024 threads per block.  A 512-thread build that shared every CU with the compares was kept as a knob until it
+// measured the same at 10^5 plain uniques and 38.3 against 33.9 ms on the deep workload, profiles/r09h.)
+constexpr int TAIL_BS = 1024;
 struct TailDev {
   std::once_flag once;
   int ncu = 64;
-  int cap[2] = {-1, -1};            // [0]: 1024-thread blocks, [1]: 512
-  bool mirror[2] = {false, false};  // the launch may carry the mirror's LDS behind TailLds (tail_lds_bytes(true) fits a workgroup of this part)
+  int cap = -1;
+  bool mirror = false;              // the launch may carry the mirror's LDS behind TailLds (tail_lds_bytes(true) fits a workgroup of this part)
 };
 static TailDev &tail_dev(int device) {
   static TailDev devs[64];
@@ -382,42 +385,40 @@ static TailDev &tail_dev(int device) {
     hipDeviceProp_t prop;
     const bool have_prop = hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0;
     if (have_prop) d.ncu = prop.multiProcessorCount;
-    for (int w = 0; w < 2; w++) {
-      const void *fn = w ? (const void *)k3_tail<512> : (const void *)k3_tail<1024>;
-      const int bs = w ? 512 : 1024;
-      const size_t lds_m = w ? tail_lds_bytes<512>(true) : tail_lds_bytes<1024>(true), lds_0 = w ? tail_lds_bytes<512>(false) : tail_lds_bytes<1024>(false);
-      // with the mirror if the part's LDS takes it (160 KB per workgroup on gfx950), else without
-      size_t lds = lds_m;
-      d.mirror[w] = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m) == hipSuccess;
-      if (d.mirror[w]) {
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, bs, lds_m) == hipSuccess && per_cu <= 0) d.mirror[w] = false;   // (accepted but not resident)
-      }
-      if (!d.mirror[w]) {
-        (void)hipGetLastError();
-        lds = lds_0;
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_0) != hipSuccess) { (void)hipGetLastError(); d.cap[w] = 0; continue; }
-      }
+    const void *fn = (const void *)k3_tail<TAIL_BS>;
+    const size_t lds_m = tail_lds_bytes<TAIL_BS>(true), lds_0 = tail_lds_bytes<TAIL_BS>(false);
+    // with the mirror if the part's LDS takes it (160 KB per workgroup on gfx950), else without
+    size_t lds = lds_m;
+    bool settable = true;
+    d.mirror = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m) == hipSuccess;
+    if (d.mirror) {
       int per_cu = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, bs, lds) != hipSuccess || !have_prop) { (void)hipGetLastError(); d.cap[w] = -1; continue; }
-      d.cap[w] = std::max(0, per_cu) * d.ncu;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, TAIL_BS, lds_m) == hipSuccess && per_cu <= 0) d.mirror = false;   // (accepted but not resident)
     }
+    if (!d.mirror) {
+      (void)hipGetLastError();
+      lds = lds_0;
+      settable = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_0) == hipSuccess;
+    }
+    int per_cu = 0;
+    if (!settable) { (void)hipGetLastError(); d.cap = 0; }
+    else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, TAIL_BS, lds) != hipSuccess || !have_prop) { (void)hipGetLastError(); d.cap = -1; }
+    else d.cap = std::max(0, per_cu) * d.ncu;
     if (have_cur && cur != device) (void)hipSetDevice(cur);
   });
   return d;
 }
-int tail_resident_max(int device, int bs) { return tail_dev(device).cap[bs == 512 ? 1 : 0]; }
-int tail_mirror_cap(int device, int bs) { return tail_dev(device).mirror[bs == 512 ? 1 : 0] ? MIR_CAP : 0; }
+int tail_resident_max(int device) { return tail_dev(device).cap; }
+int tail_mirror_cap(int device) { return tail_dev(device).mirror ? MIR_CAP : 0; }
 int tail_grid(int N, int device) {
-  // one block (of 1024 or 512 threads) per CU at most (they have to be co-resident); 4096 uniques per block at 10^6 uniques
+  // one block per CU at most (they have to be co-resident); 4096 uniques per block at 10^6 uniques
   const int want = (N + 4095) / 4096;
   return std::max(1, std::min(want, tail_dev(device).ncu));
 }
-void launch3_tail(const Eng2 &E, int grid, int bs, bool first, int ordinal, uint32_t init_reads, hipStream_t st) {
+void launch3_tail(const Eng2 &E, int grid, bool first, int ordinal, uint32_t init_reads, hipStream_t st) {
   BudKey init{1.0, init_reads};
   int dev_ = 0;
   (void)hipGetDevice(&dev_);
-  (void)tail_dev(dev_);                                    // (the dynamic-LDS attribute of both instances is set there)
-  if (bs == 512) hipLaunchKernelGGL(k3_tail<512>, dim3(grid), dim3(512), tail_lds_bytes<512>(E.mirror_on != 0), st, E, init, first ? 1 : 0, ordinal);
-  else hipLaunchKernelGGL(k3_tail<1024>, dim3(grid), dim3(1024), tail_lds_bytes<1024>(E.mirror_on != 0), st, E, init, first ? 1 : 0, ordinal);
+  (void)tail_dev(dev_);                                    // (the kernel's dynamic-LDS attribute is set there)
+  hipLaunchKernelGGL(k3_tail<TAIL_BS>, dim3(grid), dim3(TAIL_BS), tail_lds_bytes<TAIL_BS>(E.mirror_on != 0), st, E, init, first ? 1 : 0, ordinal);
 }

@@ -320,7 +320,6 @@ _SEEDED = ((7001, 6000, 200, 48), (7002, 20000, 250, 96))
     {"DADA2HIP_V2_CHAIN": "2", "DADA2HIP_NODE_CAP": "1"}, # comparison store starts at N + 16 blocks: growth through H2_CAPACITY
     {"DADA2HIP_V2_ALIGN": "commit"},                      # each centre's pairs aligned when its round commits (the long-read mode)
     {"DADA2HIP_V2_LITE": "0"},                            # every chain carries the batch compare's launches (no H2_NEED_COMPARE)
-    {"DADA2HIP_V2_GRAPH": "1", "DADA2HIP_V2_NBUF": "2"},  # hipGraph replay of both chain forms, frequent evictions
     # round 4: the persistent tail is the default above; here with several blocks on small samples, with pauses (movers that
     # do not fit the result block), a lagging host (ring limit), a tiny product buffer (in-kernel lambda for the overflow) -
     # and the launch chains, which the settings above that name chain knobs no longer reach by themselves
@@ -348,7 +347,6 @@ _SEEDED = ((7001, 6000, 200, 48), (7002, 20000, 250, 96))
     # without its pointer-free first pass (every pair through the full kernel) - what the defaults above must agree with
     {"DADA2HIP_SCREEN_BITS": "0", "DADA2HIP_AD_FAST": "0"},
     {"DADA2HIP_SCREEN_BITS": "0", "DADA2HIP_V2_TAIL": "chain"},
-    {"DADA2HIP_V3_BLOCK": "512"},                         # round 5's tail under the overlap: 512-thread blocks beside the compares on every CU
     {"DADA2HIP_V3_SPEC_MAX": "3", "DADA2HIP_V3_GRID": "5", "DADA2HIP_V3_PF_EARLY": "0"},
     # the XCD-hierarchical grid barrier (default from 48 blocks on) forced onto small grids, and the flat one forced onto the defaults
     {"DADA2HIP_V3_XBAR": "1", "DADA2HIP_V3_GRID": "9"},
@@ -356,26 +354,23 @@ _SEEDED = ((7001, 6000, 200, 48), (7002, 20000, 250, 96))
     {"DADA2HIP_V3_XBAR": "0"},
     # round 6: the tail's LDS mirror of the per-unique facts its sweeps ask for (default: on) - off, and on with the check that
     # compares it with the state arrays at the end of every round (several blocks; attempts, void attempts and plain calls mixed;
-    # 512-thread blocks; pauses and launches left for prefetches: the mirror is refilled at every launch entry)
+    # pauses and launches left for prefetches: the mirror is refilled at every launch entry)
     {"DADA2HIP_V3_MIRROR": "0"},
     {"DADA2HIP_V3_MIRROR": "2"},
     {"DADA2HIP_V3_MIRROR": "2", "DADA2HIP_V3_GRID": "5", "DADA2HIP_V3_SPEC_MAX": "3", "DADA2HIP_V2_MOV_INLINE": "64"},
-    {"DADA2HIP_V3_MIRROR": "2", "DADA2HIP_V3_GRID": "3", "DADA2HIP_V3_BLOCK": "512", "DADA2HIP_V3_PF_WAIT_US": "0", "DADA2HIP_V2_NBUF": "4"},
-    # ... the host's replay of the published moves and births on a second host thread (the replay lane: not the default), with
-    # halts that hand the mirror back to the boundary thread (host decisions, pauses, growth); and two persistent launches in flight
-    {"DADA2HIP_V3_LANE": "1"},
-    {"DADA2HIP_V3_LANE": "1", "DADA2HIP_V3_GRID": "4", "DADA2HIP_V2_MOV_INLINE": "64", "DADA2HIP_NODE_CAP": "1", "DADA2HIP_V3_RING": "2"},
+    {"DADA2HIP_V3_MIRROR": "2", "DADA2HIP_V3_GRID": "3", "DADA2HIP_V3_PF_WAIT_US": "0", "DADA2HIP_V2_NBUF": "4"},
+    # ... and two persistent launches in flight
     {"DADA2HIP_V2_DEPTH": "2"},
     # the host's replay orders EVERY mover list with its radix sort (by default only lists of 4 096 movers and more)
     {"DADA2HIP_REPLAY_RADIX_MIN": "1"},
-], ids=["classic", "v2", "v2-nbuf1", "v2-depth1", "v2-depth3", "v2-chain1", "v2-chain2-grow", "v2-align-commit", "v2-nolite", "v2-graph",
+], ids=["classic", "v2", "v2-nbuf1", "v2-depth1", "v2-depth3", "v2-chain1", "v2-chain2-grow", "v2-align-commit", "v2-nolite",
         "tail-grid7-pauses-ring2-fcap", "chains", "chains-chain1-biglists", "chains-nolite-commit",
         "tail-serial", "overlap-host-launched", "overlap-sync-grid5", "overlap-leave-at-once-nbuf4",
-        "evaluate-on-every-call", "evaluate-on-every-call-grid6-serial", "evaluate-apart", "attempts-and-plain-calls-mixed", "exact-screen-full-aligner", "exact-screen-chains", "tail-512-thread-blocks",
+        "evaluate-on-every-call", "evaluate-on-every-call-grid6-serial", "evaluate-apart", "attempts-and-plain-calls-mixed", "exact-screen-full-aligner", "exact-screen-chains",
         "attempts-and-plain-calls-mixed-grid5",
         "xcd-barrier-grid9", "xcd-barrier-grid64-pauses", "flat-barrier",
-        "no-mirror", "mirror-checked", "mirror-checked-grid5-mixed-calls-pauses", "mirror-checked-grid3-512-leaves-for-prefetches",
-        "replay-lane", "replay-lane-grid4-pauses-growth-ring2", "two-launches-in-flight", "replay-radix-sort-always"])
+        "no-mirror", "mirror-checked", "mirror-checked-grid5-mixed-calls-pauses", "mirror-checked-grid3-leaves-for-prefetches",
+        "two-launches-in-flight", "replay-radix-sort-always"])
 def test_round_engines_agree_with_the_reference(env):
     """Every engine configuration must reproduce the goldens the reference produced, the oracle on two seeded samples (6 k and
     20 k uniques: dozens of rounds, multi-shuffle rounds, cache hits and misses) and the reference's own work counters."""

@@ -43,7 +43,6 @@ def main():
     for seq in [int(x) for x in a.seqs.split(",")]:
         path = f"/tmp/d2trace_{seq}.bin"
         os.environ["DADA2HIP_V2_TRACE"] = f"{seq}:{path}"
-        os.environ["DADA2HIP_V2_GRAPH"] = "1"
         r = s.run(err, opts)
         t = np.fromfile(path, dtype=np.uint64).reshape(8, TB, 8).astype(np.float64)
         rec = {"round_block_seq": seq, "partitions_total": int(r.nclust), "kernels": {}}
