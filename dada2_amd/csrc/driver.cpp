@@ -588,6 +588,24 @@ struct BudKeyH { double p; uint32_t reads; uint32_t pad; };
 // (measured up to 1e6 alignments: 1M-unique pass 358 -> 349 ms; beyond 4e6 untested, the lane kernel takes over)
 constexpr int COOP_BATCH_LIMIT = 4000000;
 
+// Which aligner one b_compare round of a sample takes (compare_round and dada2hip_sample_compare ask here, so DADA2HIP_NW_KERNEL
+// means the same kernel in both): the anti-diagonal kernel k_nw_ad where its LDS layout applies and the batch is small enough
+// (`small_batch`: the caller's own limit), else the wide anti-diagonal kernel k_nw_adw for band windows too wide for the LDS-pointer
+// kernel (ragged long reads: eight cells per lane, pointers in HBM), else the lane kernels k_nw<WMAX> / k_nw_gen.
+enum RoundAligner { ALIGNER_LANE, ALIGNER_COOP, ALIGNER_WIDE };
+static RoundAligner choose_round_aligner(const SampleDev &D, const AlignParams &ap, int wclass, bool small_batch) {
+  const int f = knobs().nw_kernel;
+  const bool coop_ok = nw_ad_lds_bytes(D, ap) > 0 && nw_ad_lds_bytes(D, ap) <= 150 * 1024;
+  bool coop = coop_ok && small_batch;
+  if (f == NWK_LANE) coop = false;
+  if (f == NWK_COOP && coop_ok) coop = true;
+  bool wide = !coop && nw_adw_ok(D, ap) && nw_adw_lds_bytes(D, ap) <= 150 * 1024 && wclass != 33 && wclass != 65 &&
+              D.N < (1 << 20);
+  if (f == NWK_LANE) wide = false;
+  if (f == NWK_WIDE) wide = nw_adw_ok(D, ap) && nw_adw_lds_bytes(D, ap) <= 150 * 1024;
+  return wide ? ALIGNER_WIDE : (coop ? ALIGNER_COOP : ALIGNER_LANE);
+}
+
 struct Run {
   dada2hip_sample *s;
   dada2hip_opts o;
@@ -926,17 +944,9 @@ struct Run {
     // thousand (cooperative kernel).
     const int evn_i = ev_begin(EV_NW, timed, spec, /*big=*/ci == 0);
     spec_ev_nw = spec ? evn_i : -1;
-    const int f = knobs().nw_kernel;
-    const bool coop_ok = nw_ad_lds_bytes(D, ap) > 0 && nw_ad_lds_bytes(D, ap) <= 150 * 1024;
-    bool coop = coop_ok && (ci != 0 || N < COOP_BATCH_LIMIT);
-    if (f == NWK_LANE) coop = false;
-    if (f == NWK_COOP && coop_ok) coop = true;
-    // band windows too wide for the LDS-pointer kernel (ragged long reads): eight cells per lane, pointers in HBM
-    bool wide = !coop && nw_adw_ok(D, ap) && nw_adw_lds_bytes(D, ap) <= 150 * 1024 && wclass != 33 && wclass != 65 &&
-                N < (1 << 20);
-    if (f == NWK_LANE) wide = false;
-    if (f == NWK_WIDE) wide = nw_adw_ok(D, ap) && nw_adw_lds_bytes(D, ap) <= 150 * 1024;
-    if (coop && !wide)   // the gapless pairings of the round share the kernel's factor/product tail
+    const RoundAligner al = choose_round_aligner(D, ap, wclass, ci != 0 || N < COOP_BATCH_LIMIT);
+    const bool wide = al == ALIGNER_WIDE;
+    if (al == ALIGNER_COOP)   // the gapless pairings of the round share the kernel's factor/product tail
       launch_nw_ad(D, centre, nullptr, s->d_nw_list.p, ctr, 0, s->d_gl_list.p, ctr + 1, ap, s->d_err.p, s->d_lambda.p,
                    s->d_ham.p, nullptr, 0, 0, spec ? d_next.p : nullptr, stq);
     else {
@@ -3029,15 +3039,15 @@ int dada2hip_sample_compare(dada2hip_sample *s, int32_t centre, const double *er
       for (int i = 0; i < N; i++) { run.st.nshroud += hc[i] == CLS_SHROUD; run.st.nskipped += hc[i] == CLS_SKIP; }
     }
     if (n_nw > 0) {
-      const int f = knobs().nw_kernel;
-      const bool coop_ok = nw_ad_lds_bytes(D, run.ap) > 0 && nw_ad_lds_bytes(D, run.ap) <= 150 * 1024;
-      bool coop = coop_ok && n_nw < 65536;
-      if (f == NWK_LANE) coop = false;
-      if (f == NWK_COOP && coop_ok) coop = true;
+      const RoundAligner al = choose_round_aligner(D, run.ap, run.wclass, n_nw < 65536);
+      if (al == ALIGNER_WIDE) ensure_adw_scratch(s, run.ap);   // (before the timed launch)
       D2_HIP(hipEventRecord(s->ev0, stq));
-      if (coop)
+      if (al == ALIGNER_COOP)
         launch_nw_ad(D, centre, nullptr, s->d_nw_list.p, nullptr, n_nw, nullptr, nullptr, run.ap, s->d_err.p, s->d_lambda.p,
                      s->d_ham.p, nullptr, 0, 0, nullptr, stq);
+      else if (al == ALIGNER_WIDE)
+        launch_nw_adw(D, centre, nullptr, s->d_nw_list.p, nullptr, n_nw, run.ap, s->d_err.p, s->scr_adw.p, s->scr_adw_wpw,
+                      s->scr_adw_waves, s->d_lambda.p, s->d_ham.p, nullptr, 0, 0, stq);
       else {
         ensure_scratch(s, run.ap.band);
         launch_nw(D, run.wclass, centre, nullptr, s->d_nw_list.p, nullptr, n_nw, run.ap, s->d_err.p, s->scr, s->d_lambda.p,
@@ -3059,6 +3069,13 @@ int dada2hip_sample_compare(dada2hip_sample *s, int32_t centre, const double *er
     D2_HIP(hipGetLastError());
     if (stats) *stats = run.st;
   });
+}
+
+int32_t dada2hip_launch_ledger(uint64_t *mask, int32_t nwords, int32_t clear) {
+  uint64_t w[LEDGER_WORDS];
+  ledger_read(w, clear != 0);
+  for (int i = 0; i < nwords && mask; i++) mask[i] = i < LEDGER_WORDS ? w[i] : 0;
+  return LEDGER_WORDS;
 }
 
 int dada2hip_calc_pA(int32_t n, const int32_t *reads, const double *E_reads, const uint8_t *prior, int32_t device,

@@ -201,6 +201,20 @@ void launch_screen(const SampleDev &S, int centre, const ScreenParams &sp, const
 void launch_gapless(const SampleDev &S, int centre, const int32_t *d_chunk_centre, const int32_t *d_work,
                     const int32_t *d_nwork, int nwork_host, const AlignParams &ap, const double *d_err,
                     double *d_lambda, uint32_t *d_ham, uint16_t *d_view, int LV, int view_by_chunk, hipStream_t st);
+
+// Launch ledger (dada2hip_launch_ledger, include/dada2hip.h): every aligner / gapless launcher ORs the bit of the instance it
+// chose into a process-wide mask, at the place where it chooses it.  Host side only, one relaxed atomic OR per launch.
+enum {
+  LEDGER_AD = 0,         // word 0: k_nw_ad:  8 gl + 4 edge + mode (0 default, 1 generic, 2 homopolymer, 3 FAST), gl = 0 / 1 / 2 for 21 / 32 / 64 lanes
+  LEDGER_AD_LR = 32,     // word 0: k_nw_ad<.., LR> (bimera mode): 32 + 4 gl + 2 edge + generic
+  LEDGER_ADW = 64,       // word 1: k_nw_adw: 64 + 2 gl + generic
+  LEDGER_NW = 72,        // word 1: k_nw<WMAX>: 72 + 3 c + form (0 plain, 1 non-plain, 2 centre per pair), c = 0..4 for WMAX 33 / 65 / 129 / 193 / 257
+  LEDGER_NW_GEN = 88,    // word 1: k_nw_gen: 88 + (centre per pair)
+  LEDGER_GAPLESS = 96,   // word 1: k_gapless, 97: k_gapless_batch
+  LEDGER_WORDS = 2
+};
+void ledger_note(int bit);
+void ledger_read(uint64_t *out, bool clear);
 void launch_pair_class(const SampleDev &S, const int32_t *d_pc, const int32_t *d_pr, int n, const ScreenParams &sp,
                        uint8_t *d_out, hipStream_t st);
 

@@ -10,6 +10,7 @@
 //                                                                        nwalign_vectorized.cpp:71-318, nwalign_endsfree.cpp:76-216
 //   k_calc_pA       calc_pA                                              pval.cpp:44-64
 //   k_final_*       b_make_transition_by_quality_matrix / b_make_cluster_quality_matrix   error.cpp:131-172, :225-258
+#include <atomic>
 #include <cstring>
 
 #include "engine.h"
@@ -19,6 +20,14 @@
 #include "ppois.h"
 
 namespace d2 {
+
+// the launch ledger (engine.h): which compiled instance each launcher below chose, as the launcher saw it
+static std::atomic<uint64_t> g_ledger[LEDGER_WORDS];
+void ledger_note(int bit) { g_ledger[bit >> 6].fetch_or((uint64_t)1 << (bit & 63), std::memory_order_relaxed); }
+void ledger_read(uint64_t *out, bool clear) {
+  for (int w = 0; w < LEDGER_WORDS; w++)
+    out[w] = clear ? g_ledger[w].exchange(0, std::memory_order_relaxed) : g_ledger[w].load(std::memory_order_relaxed);
+}
 
 static __device__ __forceinline__ uint32_t base_at(const uint32_t *__restrict__ row, int p) {
   return (row[p >> 4] >> ((p & 15) << 1)) & 3u;
@@ -368,6 +377,7 @@ void launch_gapless(const SampleDev &S, int centre, const int32_t *d_chunk_centr
   int maxwork = d_nwork ? S.N : nwork_host;
   if (maxwork <= 0) return;
   int grid = std::min((maxwork + 255) / 256, 2048);
+  ledger_note(LEDGER_GAPLESS);
   hipLaunchKernelGGL(k_gapless, dim3(grid), dim3(256), (size_t)16 * ap.ncol * sizeof(double), st, S, centre,
                      d_chunk_centre, d_work, d_nwork, nwork_host, ap, d_err, d_lambda, d_ham, d_view, LV, view_by_chunk);
 }
@@ -421,6 +431,7 @@ __global__ __launch_bounds__(256) void k_gapless_batch(SampleDev S, NwBatch b, A
 void launch_gapless_batch(const SampleDev &S, const NwBatch &b, const AlignParams &ap, const double *d_err, double *d_lambda,
                           uint32_t *d_ham, const int32_t *d_stop_dev, hipStream_t st) {
   const int grid = std::min((S.N + 255) / 256 + KB_MAX, 2048);
+  ledger_note(LEDGER_GAPLESS + 1);
   hipLaunchKernelGGL(k_gapless_batch, dim3(grid), dim3(256), (size_t)16 * ap.ncol * sizeof(double), st, S, b, ap, d_err, d_lambda, d_ham,
                      d_stop_dev);
 }
@@ -1584,6 +1595,7 @@ void launch_nw_ad(const SampleDev &S, int centre, const int32_t *d_chunk_centre,
   do {                                                                                                                   \
     static std::atomic<size_t> attr_set[64];                                                                             \
     set_lds((const void *)k_nw_ad<GLV, DEFV, EDGEV, false, HOMOV, FASTV>, attr_set);                                     \
+    ledger_note(LEDGER_AD + 8 * (GLV == 21 ? 0 : GLV == 32 ? 1 : 2) + 4 * (EDGEV ? 1 : 0) + (FASTV ? 3 : HOMOV ? 2 : DEFV ? 0 : 1)); \
     hipLaunchKernelGGL((k_nw_ad<GLV, DEFV, EDGEV, false, HOMOV, FASTV>), dim3(grid), dim3(256), lds, st, a, d_gl_work, d_gl_nwork, G);  \
   } while (0)
 #define D2_LAUNCH_AD2(GLV, FASTV)                                                                                        \
@@ -1645,6 +1657,7 @@ void launch_nw_ad_lr(const SampleDev &S, const int32_t *d_chunk_centre, const in
       (void)hipFuncSetAttribute((const void *)k_nw_ad<GLV, DEFV, EDGEV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
       attr_set[dev_ & 63] = lds;                                                                                         \
     }                                                                                                                    \
+    ledger_note(LEDGER_AD_LR + 4 * (GLV == 21 ? 0 : GLV == 32 ? 1 : 2) + 2 * (EDGEV ? 1 : 0) + (DEFV ? 0 : 1));          \
     hipLaunchKernelGGL((k_nw_ad<GLV, DEFV, EDGEV, true>), dim3(grid), dim3(256), lds, st, a, (const int32_t *)nullptr,   \
                        (const int32_t *)nullptr, G);                                                                     \
   } while (0)
@@ -2045,6 +2058,7 @@ void launch_nw_adw(const SampleDev &S, int centre, const int32_t *d_chunk_centre
       (void)hipFuncSetAttribute((const void *)k_nw_adw<GLV, DEFV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
       attr_set[dev_ & 63] = lds;                                                                                          \
     }                                                                                                                     \
+    ledger_note(LEDGER_ADW + 2 * (GLV == 21 ? 0 : GLV == 32 ? 1 : 2) + (DEFV ? 0 : 1));                                   \
     hipLaunchKernelGGL((k_nw_adw<GLV, DEFV>), dim3(grid), dim3(256), lds, st, a, G);                                      \
   } while (0)
   if (G.GL == 21) { if (def) D2_LAUNCH_ADW(21, true); else D2_LAUNCH_ADW(21, false); }
@@ -2096,6 +2110,7 @@ void launch_nw(const SampleDev &S, int wclass, int centre, const int32_t *d_chun
   size_t lds = (size_t)16 * ap.ncol * sizeof(double);
 #define D2_NW_CLASS(W)                                                                                              \
   case W:                                                                                                           \
+    ledger_note(LEDGER_NW + 3 * (W == 33 ? 0 : W == 65 ? 1 : W == 129 ? 2 : W == 193 ? 3 : 4) + (d_pair_centre ? 2 : ap.plain() ? 0 : 1)); \
     if (d_pair_centre) hipLaunchKernelGGL((k_nw<W, true, false>), dim3(grid), dim3(256), lds, st, a);               \
     else if (ap.plain()) hipLaunchKernelGGL((k_nw<W, false, true>), dim3(grid), dim3(256), lds, st, a);             \
     else hipLaunchKernelGGL((k_nw<W, false, false>), dim3(grid), dim3(256), lds, st, a);                            \
@@ -2104,6 +2119,7 @@ void launch_nw(const SampleDev &S, int wclass, int centre, const int32_t *d_chun
     D2_NW_CLASS(33) D2_NW_CLASS(65) D2_NW_CLASS(129) D2_NW_CLASS(193) D2_NW_CLASS(257)
     default: {
       int Wgen = (ap.band < 0) ? (2 * S.maxlen + 1) : (2 * ap.band + (S.maxlen - S.minlen) + 1);
+      ledger_note(LEDGER_NW_GEN + (d_pair_centre ? 1 : 0));
       if (d_pair_centre) hipLaunchKernelGGL(k_nw_gen<true>, dim3(grid), dim3(256), lds, st, a, Wgen);
       else hipLaunchKernelGGL(k_nw_gen<false>, dim3(grid), dim3(256), lds, st, a, Wgen);
     }

@@ -361,6 +361,20 @@ int dada2hip_sample_compare(dada2hip_sample *s, int32_t centre, const double *er
                             double *lambda, uint32_t *hamming, uint8_t *cls, dada2hip_stats *stats,
                             char *errbuf, size_t errlen);
 
+/* Diagnostic: the launch ledger.  Every launcher of an aligner or gapless kernel ORs one bit into a process-wide mask at the
+ * place where it chooses the compiled instance (host side, one relaxed atomic OR per launch; no device work, no effect on any
+ * result).  Copies min(nwords, 2) 64-bit words to `mask` (further words are zeroed), clears the ledger when clear != 0 and
+ * returns the number of words the ledger has (2).  Bit b lives in word b / 64 at position b % 64; gl = 0 / 1 / 2 for 21 / 32 / 64
+ * lanes per alignment, EDGE = the band fills the lane group (cross-group neighbours are masked):
+ *   0 + 8 gl + 4 EDGE + mode   k_nw_ad, mode 0 default scores, 1 generic scores, 2 homopolymer gaps, 3 FAST (pointer-free pass)
+ *  32 + 4 gl + 2 EDGE + g      k_nw_ad in bimera mode (LR), g = 0 default / 1 generic scores
+ *  64 + 2 gl + g               k_nw_adw (wide band), g as above
+ *  72 + 3 c + form             k_nw<WMAX>, c = 0..4 for WMAX 33 / 65 / 129 / 193 / 257; form 0 plain, 1 non-plain (homopolymer
+ *                              gaps or global ends), 2 a centre per pair (nwvec, merge)
+ *  88 + p                      k_nw_gen, p = 1 with a centre per pair
+ *  96, 97                      k_gapless, k_gapless_batch */
+int32_t dada2hip_launch_ledger(uint64_t *mask, int32_t nwords, int32_t clear);
+
 /* Poisson tail used for the abundance p-value: calc_pA (src/pval.cpp:44-64) evaluated by the
  * device kernel for n (reads, E) pairs — for parity tests against the oracle. */
 int dada2hip_calc_pA(int32_t n, const int32_t *reads, const double *E_reads, const uint8_t *prior, int32_t device,

@@ -286,6 +286,66 @@ def test_emulated_band_geometries(emu_lib):
     _seeded_through_emulator(emu_lib, EMU_GEOMETRY_CASES, {"DADA2HIP_NW_KERNEL": "coop"})
 
 
+ALIGNER_SWEEP_JOBS = 3
+
+
+@pytest.mark.parametrize("part", range(ALIGNER_SWEEP_JOBS))
+def test_emulated_aligner_sweep_reaches_the_expected_instance_pair_by_pair(emu_lib, part):
+    """tests/aligner_cases.py, the short-read cases with a few dozen reads per centre, through dada2hip_sample_compare on the
+    emulated library: every pair's lambda bit-equal and hamming equal to the oracle's, and the launch ledger
+    (dada2hip_launch_ledger) showing exactly the instance each geometry case names: the emulated counterpart of the aligner
+    sweep in tests/test_gpu_aligner_instances.py."""
+    code = (
+        "import sys\n"
+        "sys.path[:0] = [%r, %r]\n"
+        "from dada2_amd import _lib\n"
+        "_lib.LIB_PATH = %r\n"
+        "import aligner_cases as A\n"
+        "from dada2_amd import api\n"
+        "from oracle import cport\n"
+        "cases = A.small_cases()[%d::%d]\n"
+        "seen = 0\n"
+        "for c in cases:\n"
+        "    npairs, got = A.run_case(api, cport, c, lean=True)\n"
+        "    assert npairs > 0\n"
+        "    seen |= got\n"
+        "print('aligner sweep: ok', len(cases), len(A.describe(seen)))\n"
+    ) % (ROOT, os.path.join(ROOT, "tests"), emu_lib, part, ALIGNER_SWEEP_JOBS)
+    out = _run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0 and "aligner sweep: ok" in out.stdout, out.stdout[-2000:] + out.stderr[-6000:]
+
+
+def test_emulated_bimera_mode_instances(emu_lib):
+    """The bimera mode of k_nw_ad on pair sets built to the window rows of tests/aligner_cases.py (band = max_shift), default and
+    user scores, one-off on / off, against the oracle; the ledger shows the LR instance of each row (the lane kernel of class 129
+    for the two windows past the kernel)."""
+    code = (
+        "import sys\n"
+        "sys.path[:0] = [%r, %r]\n"
+        "from dada2_amd import _lib\n"
+        "_lib.LIB_PATH = %r\n"
+        "import numpy as np\n"
+        "import aligner_cases as A\n"
+        "from dada2_amd import api\n"
+        "from oracle import cport\n"
+        "seen = 0\n"
+        "for ms, diff, bit_default, bit_generic in A.LR_ROWS:\n"
+        "    qs, ps = A.bimera_pair_set(ms, diff, seed=ms * 100 + diff, lean=True)\n"
+        "    for sc in A.LR_SCORES:\n"
+        "        for oo in (False, True):\n"
+        "            A.read_ledger()\n"
+        "            got = api.bimera_pairs(qs, ps, oo, *sc, ms)\n"
+        "            ran = A.read_ledger() & ~A.GAPLESS_BITS\n"
+        "            assert np.array_equal(got, cport.bimera_pairs(qs, ps, oo, *sc, ms)), (ms, diff, sc, oo)\n"
+        "            assert ran == (bit_default if sc == (5, -4, -8) else bit_generic), (ms, diff, A.describe(ran))\n"
+        "            seen |= ran\n"
+        "assert len(A.describe(seen)) == 13, A.describe(seen)\n"
+        "print('bimera instances: ok')\n"
+    ) % (ROOT, os.path.join(ROOT, "tests"), emu_lib)
+    out = _run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0 and "bimera instances: ok" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
+
+
 HOOKS_CODE = (
     "import sys\n"
     "sys.path[:0] = [%r, %r]\n"

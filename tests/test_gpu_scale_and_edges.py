@@ -41,7 +41,8 @@ def _mutate(rng, s, nsub=0, dels=(), ins=()):
 def test_five_prime_offsets_alignment_level(api, oracle_c, L, offsets, nw_kernel, monkeypatch):
     """One b_compare round (sub_new + compute_lambda) of suffix / prefix / indel-carrying reads against a full-length
     centre, band 32: lambda bits and hamming must equal the oracle's for every pair.  `wide` = k_nw_adw (run descriptors
-    used to hold the diagonal offset in 8 bits), `lane` = k_nw<WMAX> / k_nw_gen."""
+    used to hold the diagonal offset in 8 bits), `lane` = k_nw<WMAX> / k_nw_gen: the library's launch ledger says which one ran."""
+    import aligner_cases as A
     monkeypatch.setenv("DADA2HIP_NW_KERNEL", nw_kernel)
     rng = np.random.default_rng(L)
     centre = "".join("ACGT"[int(x)] for x in rng.integers(0, 4, size=L))
@@ -62,9 +63,13 @@ def test_five_prime_offsets_alignment_level(api, oracle_c, L, offsets, nw_kernel
     o = DadaOpts(BAND_SIZE=32)
     smp = api.Sample(seqs, ab, None, quals)
     try:
+        A.read_ledger()
         lam, ham, cls, st = smp.compare(0, err, o, kdist_cutoff=1.0)
+        ran = A.read_ledger() & ~A.GAPLESS_BITS
     finally:
         smp.close()
+    # (window W + 1 = 466 / 506 cells: 64 lanes of k_nw_adw; past every k_nw<WMAX> class)
+    assert ran == (A.bit_adw(64, False) if nw_kernel == "wide" else A.bit_gen()), (nw_kernel, A.describe(ran))
     for i in range(1, n):
         wl, wh, kd, ko = oracle_c.compare(seqs[0], quals[0, : len(seqs[0])], seqs[i], quals[i, : len(seqs[i])], err, o, kdist_cutoff=1.0)
         assert ham[i] == wh, (i, len(seqs[i]), int(ham[i]), wh)

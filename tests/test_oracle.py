@@ -217,3 +217,31 @@ def test_restated_homopolymer_path_matches_the_reference_live(oracle_c, oracle_r
         a = oracle_c.dada_uniques(d.seqs, d.abundances, None, tperr1(), d.quals, o)
         b = oracle_ref.dada_uniques(d.seqs, d.abundances, None, tperr1(), d.quals, o)
         assert_results_equal(a, b, exact_float=True)
+
+
+
+def test_restated_compare_matches_the_reference_on_the_aligner_case_table(oracle_c, oracle_ref):
+    """tests/aligner_cases.py (the short-read cases, thinned): the restatement's compare against the reference's own sub_new +
+    compute_lambda_ts, bit for bit - so the restatement and the kernels cannot share one misreading of these shapes."""
+    import aligner_cases as A
+    npairs = 0
+    for c in A.small_cases():
+        b = A.build(c, lean=True)
+        for ci in b.centres:
+            cq = b.quals[ci, : len(b.seqs[ci])]
+            for i, s in enumerate(b.seqs):
+                rq = b.quals[i, : len(s)]
+                got = oracle_c.compare(b.seqs[ci], cq, s, rq, b.err, b.opts, kdist_cutoff=1.0)
+                want = oracle_ref.compare(b.seqs[ci], cq, s, rq, b.err, b.opts, kdist_cutoff=1.0)
+                assert got[:2] == want[:2], (c.name, b.kinds[ci], b.kinds[i], got, want)
+                npairs += 1
+    assert npairs > 20000
+
+
+def test_restated_bimera_pairs_match_the_reference_on_the_aligner_case_table(oracle_c, oracle_ref):
+    import aligner_cases as A
+    for ms, diff, _, _ in A.LR_ROWS:
+        qs, ps = A.bimera_pair_set(ms, diff, seed=ms * 100 + diff)
+        for sc in A.LR_SCORES:
+            for oo in (False, True):
+                assert np.array_equal(oracle_c.bimera_pairs(qs, ps, oo, *sc, ms), oracle_ref.bimera_pairs(qs, ps, oo, *sc, ms)), (ms, diff, sc, oo)
