@@ -31,6 +31,10 @@ try:
         _, n, L, G = case.split(":")
         d = make_sample(tperr1(), int(n), L=int(L), G=int(G), seed=4242, chunk=max(4000, int(n)))
         err, pri, o = tperr1(), None, DadaOpts()
+    elif case.startswith("regime:"):     # tests/regime_cases.py: also against the oracle (and the case's facts) below
+        import regime_cases
+        d, pri, o, _ = regime_cases.build(case.split(":")[1])
+        err = tperr1()
     else:
         d, err, pri, o, exp, meta = case_inputs(case)
     smp = api.Sample.from_derep(d, pri, device=0)
@@ -62,6 +66,11 @@ try:
     # the reference's own work counters (dada.h:113-114), summed over the blocks
     assert got.stats["ncompare"] - got.stats["nskipped"] == want.stats["ncompare"] - want.stats["nskipped"]
     assert got.stats["nshroud"] == want.stats["nshroud"]
+    if case.startswith("regime:"):
+        from helpers import P_RTOL
+        from regime_runner import cached_oracle
+        name = case.split(":")[1]
+        assert_results_equal(got, regime_cases.check_facts(name, cached_oracle(name)), p_rtol=P_RTOL, check_birth_from=pri is None)
     print(f"rank {rank}/{world} ok: {got.nclust} partitions, collectives {got.stats['shard_collectives']}", flush=True)
 finally:
     dist.destroy_process_group()

@@ -120,6 +120,54 @@ def run_cases(emu_lib, names, env=None, timeout=900):
     return out.stdout
 
 
+# ---- tests/regime_cases.py: more than 1 024 partitions, long lists of exactly tied bud candidates, abundances of real magnitude ----
+# (first in the module: the crowd jobs are its longest and should be the first on the pool)
+REGIME_QUICK = "tied_65,tied_300,tied_two_groups_movers,tied_300_permuted,deep_2p16,deep_3e8,deep_3e8_priors_omega_p,deep_2p24_minfold_minabund"
+REGIME_EMU_JOBS = [
+    # the crowd (1 112 partitions: LDS tables of 1 024 entries overflow, the per-cluster arrays grow to 2 048) on the persistent tail
+    # with one block and with three, and on the launch chains
+    ("crowd_small", {}), ("crowd_small", {"DADA2HIP_V3_GRID": "3"}), ("crowd_small", {"DADA2HIP_V2_TAIL": "chain"}),
+    # tie lists of 65 / 300 / 10 + 300 candidates (past the 64 inline records), plain mode, and the deep abundances with their options
+    (REGIME_QUICK, {}), (REGIME_QUICK, {"DADA2HIP_V2_TAIL": "chain"}), (REGIME_QUICK, {"DADA2HIP_ENGINE": "classic"}),
+    # ... and of 4 200 (past the 4 096 full records the device keeps: index list + rebuild on the host)
+    ("tied_4200", {}), ("tied_5000", {}),
+]
+
+
+def test_emulated_regime_jobs_cover_the_cases_the_table_names():
+    import regime_cases
+    ran = {c for cases, env in REGIME_EMU_JOBS if not env for c in cases.split(",")}
+    assert set(regime_cases.EMU_CASES) <= ran and not ran & set(regime_cases.GPU_ONLY)
+    assert {"DADA2HIP_V2_TAIL": "chain"} in [env for cases, env in REGIME_EMU_JOBS if cases == "crowd_small"]
+
+
+@pytest.mark.parametrize("cases,env", REGIME_EMU_JOBS,
+                         ids=["crowd", "crowd-tail-grid3", "crowd-chains", "ties-and-deep", "ties-and-deep-chains", "ties-and-deep-classic-engine",
+                              "ties-4200", "ties-5000"])
+def test_emulated_regimes_match_the_oracle(emu_lib, cases, env):
+    """tests/regime_runner.py on the emulated library: each case's facts hold on the oracle (the sample reaches its regime),
+    then every output against the oracle; the stats name the engine that ran."""
+    import json
+    e = dict(os.environ)
+    e.update(env)
+    out = _run([sys.executable, os.path.join(ROOT, "tests", "regime_runner.py"), "emu", "single", cases], env=e, capture_output=True,
+               text=True, timeout=1500)
+    names = cases.split(",")
+    assert out.returncode == 0 and out.stdout.count("ok ") == len(names), out.stdout[-2000:] + out.stderr[-4000:]
+    for line in out.stdout.splitlines():
+        if not line.startswith("ok "):
+            continue
+        _, name, js = line.split(" ", 2)
+        st = json.loads(js)
+        persistent = not env and "permuted" not in name            # (input that is not abundance-sorted runs in plain mode)
+        if env.get("DADA2HIP_V3_GRID"):
+            assert st["tail_launches"] > 0 and st["tail_blocks"] == int(env["DADA2HIP_V3_GRID"]), (name, st)
+        else:
+            assert (st["tail_launches"] > 0) == persistent, (name, st)
+        if name.startswith("crowd"):
+            assert st["nclust"] > 1024 and st["nmoves"] > 1024, (name, st)
+
+
 @pytest.mark.parametrize("env", [{}, {"DADA2HIP_ENGINE": "classic"}, {"DADA2HIP_NW_KERNEL": "lane"}, {"DADA2HIP_NW_KERNEL": "wide"},
                                  {"DADA2HIP_V2_ALIGN": "commit", "DADA2HIP_V3_GRID": "2"},
                                  # the persistent round tail (k3_tail) with several co-resident blocks, with mover lists that do not

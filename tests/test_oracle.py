@@ -108,6 +108,29 @@ def test_restatement_vs_reference_live(oracle_c, oracle_ref, seed, kw):
         assert_results_equal(a, b, exact_float=True, check_birth_from=pri is None)
 
 
+def _regime_case_names():
+    import regime_cases as R
+    return list(R.CASES)
+
+
+@pytest.mark.parametrize("name", _regime_case_names())
+def test_restatement_vs_reference_live_on_the_regime_cases(oracle_c, oracle_ref, name):
+    """tests/regime_cases.py - more than 1 024 partitions, tie lists of thousands of candidates (the scan-order rule with
+    bi_pop_raw's swap-with-last), abundances up to the top of R's integer range (where $subqual and the 32-bit q * reads of
+    $clusterquals wrap) - restatement == reference, serial and multithreaded: what licenses the restatement as the checker of the
+    emulated and the -m gpu runs in these regimes.  The case's facts are asserted on the way."""
+    import regime_cases as R
+    d, pri, opts, facts = R.build(name)
+    b = R.check_facts(name)
+    for mt in (False, True):
+        a = oracle_ref.dada_uniques(d.seqs, d.abundances, pri, tperr1(), d.quals, opts, multithread=mt)
+        if mt and name not in R.GPU_ONLY:    # (the restatement's flag only changes its work counters: not run twice on the largest case)
+            b = oracle_c.dada_uniques(d.seqs, d.abundances, pri, tperr1(), d.quals, opts, multithread=True)
+        assert_results_equal(a, b, exact_float=True, check_birth_from=pri is None)
+    if "subqual_and_the_q_times_reads_product_wrap" in facts:
+        assert (a.subqual < 0).any() and np.array_equal(a.clusterquals, b.clusterquals, equal_nan=True)
+
+
 def test_restatement_vs_reference_reads_longer_than_2047(oracle_c, oracle_ref):
     """2.1-2.3 kb reads (PacBio-style qualities, band 32): the checker of the -m gpu long-read case, pinned to the reference."""
     d, err = long_read_sample()
