@@ -290,6 +290,25 @@ def test_emulated_merge_pairs_goldens_with_packed_pairs(emu_lib):
     assert out.returncode == 0 and "merge goldens: ok" in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
 
 
+def test_emulated_merge_pairs_on_the_constructed_cases(emu_lib):
+    """tests/merge_cases.py's constructed regimes (overlap and mismatch thresholds, overhangs, containment, prefer, repeats,
+    2 x 300 nt, no pair left) and the 66 000-pair case that crosses the 65 536-pair chunk of dada2hip_merge_pairs, on the
+    emulated library against the oracle's rows; the ledger shows k_nw_gen<pair> only."""
+    code = (
+        "import sys\n"
+        "sys.path[:0] = [%r, %r]\n"
+        "from dada2_amd import _lib\n"
+        "_lib.LIB_PATH = %r\n"
+        "import test_merge as T\n"
+        "cases = T.CONSTRUCTED + [T._the_large_case()]\n"
+        "for c in cases:\n"
+        "    T.run_constructed(c)\n"
+        "print('constructed merge cases: ok', len(cases))\n"
+    ) % (ROOT, os.path.join(ROOT, "tests"), emu_lib)
+    out = _run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0 and "constructed merge cases: ok 10" in out.stdout, out.stdout[-2000:] + out.stderr[-6000:]
+
+
 def _seeded_through_emulator(emu_lib, cases, env=None, timeout=1500):
     code = (
         "import sys\n"
@@ -361,6 +380,59 @@ def test_emulated_aligner_sweep_reaches_the_expected_instance_pair_by_pair(emu_l
     ) % (ROOT, os.path.join(ROOT, "tests"), emu_lib, part, ALIGNER_SWEEP_JOBS)
     out = _run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0 and "aligner sweep: ok" in out.stdout, out.stdout[-2000:] + out.stderr[-6000:]
+
+
+PAIR_EXPORT_JOBS = 2
+
+
+@pytest.mark.parametrize("part", range(PAIR_EXPORT_JOBS))
+def test_emulated_pairwise_exports_reach_the_expected_pair_instance(emu_lib, part):
+    """tests/pair_cases.py, the thinned table (batches of at most 65 pairs, reads of at most 130 nt; every pair instance with
+    ends free and global, the homopolymer-gap pairs through dada2hip_nwalign, strings of 2-5 nt) on the emulated library: both
+    gapped strings of every pair equal to the oracle's, eight pairs of each batch alone as well, the launch ledger showing exactly
+    the pair instance each case names: the emulated counterpart of tests/test_gpu_pairwise_exports.py.  All six pair instances
+    run in each job."""
+    code = (
+        "import sys\n"
+        "sys.path[:0] = [%r, %r]\n"
+        "from dada2_amd import _lib\n"
+        "_lib.LIB_PATH = %r\n"
+        "import pair_cases as P\n"
+        "from dada2_amd import api\n"
+        "from oracle import cport\n"
+        "vec = [c for c in P.small_vec_cases() if not c.letters][%d::%d]\n"
+        "al = P.small_align_cases()[%d::%d]\n"
+        "seen = 0\n"
+        "for c in vec:\n"
+        "    seen |= P.run_vec_case(api, cport, c)\n"
+        "for c in al:\n"
+        "    seen |= P.run_align_case(api, cport, c)\n"
+        "missing = [P.describe(b)[0] for b in P.pair_instances() if not seen & b]\n"
+        "assert not missing, missing\n"
+        "print('pairwise exports: ok', len(vec), len(al))\n"
+    ) % (ROOT, os.path.join(ROOT, "tests"), emu_lib, part, PAIR_EXPORT_JOBS, part, PAIR_EXPORT_JOBS)
+    out = _run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0 and "pairwise exports: ok" in out.stdout, out.stdout[-2000:] + out.stderr[-6000:]
+
+
+def test_emulated_pairwise_exports_two_plane_letters(emu_lib, oracle_ref):
+    """The two-plane case of tests/pair_cases.py (130 pairs with N / IUPAC letters: three chunks, the last ragged) against the
+    reference's own C_nwvec call on raw bytes."""
+    code = (
+        "import sys\n"
+        "sys.path[:0] = [%r, %r]\n"
+        "from dada2_amd import _lib\n"
+        "_lib.LIB_PATH = %r\n"
+        "import pair_cases as P\n"
+        "from dada2_amd import api\n"
+        "from oracle import cport, ref\n"
+        "cases = [c for c in P.vec_cases() if c.letters]\n"
+        "for c in cases:\n"
+        "    assert P.run_vec_case(api, cport, c, ref=ref) == P.bit_gen(True)\n"
+        "print('pairwise letters: ok', len(cases))\n"
+    ) % (ROOT, os.path.join(ROOT, "tests"), emu_lib)
+    out = _run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0 and "pairwise letters: ok 1" in out.stdout, out.stdout[-2000:] + out.stderr[-6000:]
 
 
 def test_emulated_bimera_mode_instances(emu_lib):

@@ -62,6 +62,9 @@ def test_compare_round_matches_reference(api, fq, band):
 
 
 def test_nwvec_matches_reference_alignments(api):
+    """400 golden pairs, one dada2hip_nwvec call per band.  The lengths inside a band run from about 20 to about 299 nt, and a
+    batch's kernel follows from the batch's length spread, so by the launch ledger EVERY one of the nine calls runs
+    k_nw_gen<pair>: the five register-class pair kernels are not reached here (tests/test_gpu_pairwise_exports.py drives them)."""
     z = np.load(os.path.join(GOLDEN, "nwalign_pairs.npz"))
     s1, s2, band = [str(x) for x in z["s1"]], [str(x) for x in z["s2"]], z["band"]
     for b in sorted(set(band.tolist())):
@@ -322,7 +325,9 @@ def test_errors_keep_reference_messages(api):
 def test_nwalign_variants_match_reference(api):
     """C_nwalign's three aligners on the device (src/evaluate.cpp:18-62): nwalign_endsfree, nwalign_endsfree_homo (a gap
     opposite a homopolymer base has its own penalty) and the global nwalign of endsfree=FALSE, on 300 homopolymer-rich
-    pairs whose alignments the reference itself produced (tests/golden/make_homo_golden.py)."""
+    pairs whose alignments the reference itself produced (tests/golden/make_homo_golden.py).  One pair per call: a single
+    active lane per wave, in whatever pair kernel the pair's own lengths and band give (by the launch ledger all six are
+    reached, k_nw<193, pair> by two pairs); whole waves of unrelated pairs are tests/test_gpu_pairwise_exports.py's."""
     z = np.load(os.path.join(GOLDEN, "nwalign_variants.npz"))
     for i in range(len(z["s1"])):
         got = api.nwalign(str(z["s1"][i]), str(z["s2"][i]), 5, -4, -8, homo_gap=int(z["homo_gap"][i]), band=int(z["band"][i]),

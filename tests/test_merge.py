@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from helpers import GOLDEN, case_inputs
-from merge_cases import OPTION_SETS, make_case
+from merge_cases import OPTION_SETS, constructed_cases, large_case, make_case
 from oracle import cport, merge as omerge
 
 KEYS = ("sequence", "abundance", "forward", "reverse", "nmatch", "nmismatch", "nindel", "prefer", "accept")
@@ -166,3 +166,83 @@ def test_whole_path_sam1_forward_reverse_merge():
     assert sum(r["abundance"] for r in got if r["accept"]) > 1000     # most of the 1 500 read pairs of the fixture merge
     ok = [r for r in api.merge_pairs(res["sam1F"], dereps["sam1F"], res["sam1R"], dereps["sam1R"])]
     assert ok == [r for r in got if r["accept"]]
+
+
+# ---- the constructed regimes (tests/merge_cases.py): thresholds, overhangs, containment, prefer, repeats, 2 x 300 nt, 66 000 pairs ----
+CONSTRUCTED = constructed_cases()
+_LARGE = {}
+_ROWS = {}
+
+
+def _the_large_case():
+    if not _LARGE:
+        _LARGE["case"] = large_case()
+    return _LARGE["case"]
+
+
+def oracle_rows(c):
+    """{option index: rows of oracle/merge.py with the plain-C restatement, rejects included}, the case's fact asserted; once per process."""
+    if c["name"] not in _ROWS:
+        rows = {k: omerge.merge_pairs(c["fwd"], c["rev"], c["seqsF"], c["n0F"], c["seqsR"], c["n0R"], cport, return_rejects=True, **o)
+                for k, o in enumerate(c["options"])}
+        c["fact"](rows)
+        _ROWS[c["name"]] = rows
+    return _ROWS[c["name"]]
+
+
+def run_constructed(c):
+    """dada2hip_merge_pairs on a constructed case under each of its option sets against the oracle's rows; the launch ledger
+    shows k_nw_gen<pair> and nothing else (nothing at all where no pair is left to align)."""
+    import aligner_cases as A
+    want = oracle_rows(c)
+    for k, o in enumerate(c["options"]):
+        A.read_ledger()
+        rc_, msg, rows = _call_merge(c, **o)
+        ran = A.read_ledger() & ~A.GAPLESS_BITS
+        assert rc_ == 0, msg
+        assert_rows_equal(rows, want[k])
+        assert ran == (A.bit_gen(True) if want[k] else 0), (c["name"], o, A.describe(ran))
+
+
+def test_constructed_cases_reach_their_regimes():
+    """Each constructed case's fact, from the oracle's rows: the overlap IS min_overlap and one less, the differences ARE
+    max_mismatch and one more, trimming changes the sequence, prefer changes the sequence, ... - and the large case has more
+    unique pairs than one device call takes, with accepted rows on both sides of the boundary."""
+    for c in CONSTRUCTED + [_the_large_case()]:
+        oracle_rows(c)
+
+
+def test_helpers_match_the_reference_on_the_constructed_alignments(oracle_c, oracle_ref):
+    """The restatement's aligner, C_eval_pair and C_pair_consensus against the reference's own on every pair of the constructed
+    cases under each case's scores (the large case: every seventh of its 66 000 pairs)."""
+    n = 0
+    for c in CONSTRUCTED + [_the_large_case()]:
+        ups = list(dict.fromkeys((int(f), int(r)) for f, r in zip(c["fwd"], c["rev"]) if f > 0 and r > 0))
+        if len(ups) > 1000:
+            ups = ups[::7] + ups[65530:65542]
+        for sc in sorted({(1, -64, -64) if o.get("max_mismatch", 0) == 0 else (1, -8, -8) for o in c["options"]}):
+            for f, r in ups:
+                a, b = c["seqsF"][f - 1], omerge.rc(c["seqsR"][r - 1])
+                a1, a2 = oracle_ref.C_nwalign(a, b, *sc, None, -1, True)
+                assert (a1, a2) == cport.C_nwalign(a, b, *sc, None, -1, True), (c["name"], f, r)
+                assert oracle_ref.eval_pair(a1, a2) == cport.eval_pair(a1, a2)
+                for prefer in (1, 2):
+                    for trim in (False, True):
+                        assert oracle_ref.pair_consensus(a1, a2, prefer, trim) == cport.pair_consensus(a1, a2, prefer, trim)
+                n += 1
+    assert n > 9000
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", CONSTRUCTED, ids=[c["name"] for c in CONSTRUCTED])
+def test_device_merge_on_the_constructed_cases(case):
+    run_constructed(case)
+
+
+@pytest.mark.gpu
+def test_device_merge_across_the_65536_pair_chunk():
+    """66 000 unique pairs: dada2hip_merge_pairs aligns them in two device calls; every row on both sides of the boundary."""
+    c = _the_large_case()
+    P = len({(int(f), int(r)) for f, r in zip(c["fwd"], c["rev"])})
+    assert P > 65536
+    run_constructed(c)

@@ -268,3 +268,60 @@ def test_restated_bimera_pairs_match_the_reference_on_the_aligner_case_table(ora
         for sc in A.LR_SCORES:
             for oo in (False, True):
                 assert np.array_equal(oracle_c.bimera_pairs(qs, ps, oo, *sc, ms), oracle_ref.bimera_pairs(qs, ps, oo, *sc, ms)), (ms, diff, sc, oo)
+
+
+def _nwvec_excluded(a, c, sc):
+    """The two stated differences between C_nwvec and C_nwalign: a second sequence of one base (nwalign_vectorized2 against
+    nwalign_endsfree), and C_nwvec's 16-bit scores ((len1 + len2) max|score| >= 32 767)."""
+    return len(c) == 1 or (len(a) + len(c)) * max(abs(x) for x in sc) >= 32767
+
+
+def test_restated_aligners_match_the_reference_on_the_pair_case_table(oracle_c, oracle_ref):
+    """tests/pair_cases.py, every case: the restatement's C_nwalign (what the GPU tests of the pairwise exports compare with)
+    against the reference's own C_nwalign, and for the nwvec cases against the reference's C_nwvec call too, less the two
+    stated exclusions - which may take at most 5 % of a case's pairs and never all pairs of a pair class.  Each batch's facts
+    (interior gaps in either string, a pair that depends on the tie order) are asserted on the way."""
+    import pair_cases as P
+    npairs = nvec = 0
+    for c in P.vec_cases():
+        b = P.build(c)
+        sc = P.SCORES[c.score]
+        want = P.expected(oracle_c, c, oracle_ref)
+        P.check_facts(oracle_c, c, want)
+        left = {}
+        nexcl = 0
+        for i, (a, s, al) in enumerate(zip(b.s1, b.s2, want)):
+            P.check_alignment(c.name, i, a, s, al)
+            left.setdefault(b.kinds[i], 0)
+            if not c.letters:
+                assert tuple(al) == tuple(oracle_ref.C_nwalign(a, s, sc[0], sc[1], sc[2], None, c.band, c.endsfree)), (c.name, i, b.kinds[i], a, s)
+                npairs += 1
+                if _nwvec_excluded(a, s, sc):
+                    nexcl += 1
+                    continue
+                assert tuple(al) == tuple(oracle_ref.nwvec_raw(a, s, sc[0], sc[1], sc[2], c.band, c.endsfree)), (c.name, i, b.kinds[i], a, s)
+                nvec += 1
+            left[b.kinds[i]] += 1
+        assert nexcl * 20 <= c.n, (c.name, "excluded from the C_nwvec comparison:", nexcl, "of", c.n)
+        assert all(v > 0 for v in left.values()), (c.name, "pair classes with no pair left:", [k for k, v in left.items() if not v])
+    for c in P.align_cases():
+        for a, s in c.pairs:
+            assert oracle_c.C_nwalign(a, s, 5, -4, -8, c.homo_gap, c.band, True) == oracle_ref.C_nwalign(a, s, 5, -4, -8, c.homo_gap, c.band, True), (c.name, a, s)
+            npairs += 1
+    assert npairs > 4000 and nvec > 4000, (npairs, nvec)
+
+
+def test_reference_global_aligners_part_below_the_band_sentinel(oracle_c, oracle_ref):
+    """the reference's global alignment of C_nwalign (band edge -9999) and of C_nwvec (band edge INT16_MIN + 64)
+    give different strings once in-band scores fall below -9999 - 1/-64/-64, 233 nt against 40 nt, band 32.  The restatement (and
+    the device) follow C_nwalign there; tests/pair_cases.py keeps its global 1/-64/-64 batches at reads of at most 105 nt."""
+    import pair_cases as P
+    rng = np.random.default_rng(258)
+    a = P._rnd(rng, 233)
+    b = a[96:136]
+    assert not _nwvec_excluded(a, b, (1, -64, -64))
+    want = oracle_ref.C_nwalign(a, b, 1, -64, -64, None, 32, False)
+    assert oracle_c.C_nwalign(a, b, 1, -64, -64, None, 32, False) == want
+    assert tuple(oracle_ref.nwvec_raw(a, b, 1, -64, -64, 32, False)) != tuple(want)
+    for ef, sc in ((True, (1, -64, -64)), (False, (1, -8, -8))):         # (ends free, or global with scores above -9999: one answer)
+        assert tuple(oracle_ref.nwvec_raw(a, b, *sc, 32, ef)) == tuple(oracle_ref.C_nwalign(a, b, *sc, None, 32, ef))
