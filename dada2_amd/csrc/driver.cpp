@@ -106,6 +106,7 @@ struct dada2hip_sample {
   uint64_t total_reads = 0;
   int qmax = 0;
   double ms_upload = 0;
+  double ms_upload_part[5] = {0, 0, 0, 0, 0};   // lengths, packing (+ its copies and the k-mer launch), quality conversion, wait side, wait main
   // per-run device work buffers (kept across runs: selfConsist passes reuse them)
   DevBuf<uint8_t> d_skip, d_cls, d_correct, d_moves;
   DevBuf<double> d_lambda, d_err;
@@ -283,12 +284,16 @@ int nw_sentinel(const dada2hip_opts &o) {
 // boundary hands over 250 MB of characters and 2 GB of doubles, so the marshalling is spread over the host pool:
 //   pass 1  strlen / abundance / prior per unique                                  (threads)
 //   pass 2  2-bit packing + ACGT validation straight into a pinned buffer          (threads)  -> one async H2D
-//   pass 3  (uint8) round(mean quality) of raw_new (containers.cpp:34), chunk-wise into pinned bytes (threads) -> H2D per
-//           chunk on the side stream, overlapping the next chunk's conversion and the k-mer build on the main stream
+//   pass 3  (uint8) round(mean quality) of raw_new (containers.cpp:34) into pinned bytes, ONE job over all rows (threads);
+//           each 16 MB chunk goes out on the side stream when its last piece is done, overlapping the conversion of the
+//           chunks behind it and the k-mer build on the main stream
+// Passes 2 and 3 run hostsimd.cpp's loops (explicit AVX2 where the CPU has it).
 // lite = nwalign / nwvec helper samples: no qualities, no k-mer records, any length >= 1.
 void sample_create(dada2hip_sample *s, int32_t nraw, const char *const *seqs, const int32_t *abund,
                    const uint8_t *priors, const double *quals, int32_t quals_nrow, int device, bool lite = false) {
   auto t0 = clk::now();
+  auto t_lap = t0;
+  auto lap = [&](int k) { s->ms_upload_part[k] = ms_since(t_lap); t_lap = clk::now(); };   // (DADA2HIP_V2_SUMMARY: the upload's split)
   if (nraw <= 0) throw InputError{"Zero input sequences."};
   if (!seqs || !abund) throw InputError{"Sequence and abundance vectors had different lengths."};
   s->h_len.resize(nraw);
@@ -315,6 +320,7 @@ void sample_create(dada2hip_sample *s, int32_t nraw, const char *const *seqs, co
   });
   const int maxlen = amax.load(), minlen = amin.load();
   s->total_reads = atot.load();
+  lap(0);
   if (maxlen >= SEQLEN) throw InputError{"Input sequences exceed the maximum allowed string length."};
   if (!lite) {
     if (minlen <= KMER_SIZE) throw InputError{"Input sequences must all be longer than the kmer-size (5)."};
@@ -344,28 +350,9 @@ void sample_create(dada2hip_sample *s, int32_t nraw, const char *const *seqs, co
   const int W2 = D.W2;
   uint32_t *packed = s->h_seq2.p;
   parallel_for((size_t)nraw, 2048, [&](size_t lo, size_t hi) {
-    for (size_t i = lo; i < hi; i++) {
-      const char *q = seqs[i];
-      uint32_t *row = packed + i * W2;
-      const int l = s->h_len[i];
-      int p = 0;
-      for (int w = 0; w < W2; w++) {
-        uint32_t word = 0;
-        const int e = std::min(l - p, 16);
-        for (int k = 0; k < e; k++, p++) {
-          uint32_t c;
-          switch (q[p]) {
-            case 'A': c = 0; break;
-            case 'C': c = 1; break;
-            case 'G': c = 2; break;
-            case 'T': c = 3; break;
-            default: c = 0; bad.store(1, std::memory_order_relaxed);
-          }
-          word |= c << (k << 1);
-        }
-        row[w] = word;
-      }
-    }
+    uint32_t any = 0;                                            // one accumulator per piece, no store per base
+    for (size_t i = lo; i < hi; i++) any |= d2::pack_row_2bit(seqs[i], s->h_len[i], packed + i * W2, W2);
+    if (any) bad.store(1, std::memory_order_relaxed);
   });
   if (bad.load()) throw InputError{"Invalid derep$uniques vector. Sequences must be made up only of A/C/G/T."};
   s->seq2.alloc((size_t)nraw * D.W2);
@@ -406,6 +393,7 @@ void sample_create(dada2hip_sample *s, int32_t nraw, const char *const *seqs, co
     D.kbits = s->kbits.p; D.kmult = s->kmult.p;
   } else { D.kbits = nullptr; D.kmult = nullptr; }
   launch_build_kmers(D, s->stream);          // overlaps the quality upload below (side stream)
+  lap(1);
 
   // qualities: raw_new's (uint8) round(mean quality) (containers.cpp:34) is part of the marshalling here as it is in the
   // reference: the host pool turns the R double matrix (8 B per base, 2 GB at 10^6 uniques) into the byte matrix the
@@ -418,22 +406,41 @@ void sample_create(dada2hip_sample *s, int32_t nraw, const char *const *seqs, co
     std::atomic<int> badq{0}, qmax{0};
     // Several samples in flight on this device (dada2hip_run_multi's threads share it: active_runs() is raised for the call): half
     // the pool per upload.  The uploads of the samples go through the pool one after the other and overlap the OTHER samples'
-    // rounds, so their wall time is not what counts - 64 threads read the matrix at 80 GB/s for 1.6 CPU-seconds per 2 GB, 32 at
-    // 60 GB/s for 1.1, and they leave the memory system and the container's CPU quota to the threads that feed the
-    // device: configs[3] on one GPU, three in flight, 64 / 32 / 24 / 16 threads: 187 / 174 / 183 / 193 ms (profiles/r10u_*).
+    // rounds, so their wall time is not what counts, the CPU time they take from the threads that feed the device is (the
+    // container's CPU quota): configs[3] on one GPU, three in flight, 64 / 32 / 24 / 16 threads: 187 / 174 / 183 /
+    // 193 ms (profiles/r10u_*).  What the host can do with the 2 GB matrix, in one container of sixteen CPUs' quota
+    // (tools/host_marshal, profiles/r12a_host_marshal.txt): a plain vector sum reads it at 278 / 577 / 359 GB/s on 16 / 32 / 64
+    // threads, the AVX2 conversion at 185 / 359 / 272, the scalar one at 147 / 260 / 280.
     const int marshal_threads = active_runs(device).load() > 1 ? std::max(8, HostPool::get().nthreads() / 2) : 0;
-    const size_t rows_per = std::max<size_t>(1, ((size_t)16 << 20) / (size_t)LQ);
-    for (size_t r0 = 0; r0 < (size_t)nraw; r0 += rows_per) {
-      const size_t nr = std::min<size_t>(rows_per, nraw - r0);
-      parallel_for(nr, 512, [&](size_t lo, size_t hi) {
-        int mx = 0, bad = 0;
-        for (size_t r = r0 + lo; r < r0 + hi; r++) {
+    // One job over all rows (a fork-join per chunk left every thread two pieces and a barrier sixteen times over).  A chunk is
+    // whole pieces of 512 rows, about 16 MB; a countdown per chunk tells the thread that finishes its last rows, and that thread
+    // queues the chunk's copy - the copies go out in chunk order, under a lock that is taken once per chunk.
+    const size_t grain = 512;
+    const size_t rows_per = std::max<size_t>(1, ((size_t)16 << 20) / (size_t)LQ / grain) * grain;
+    const size_t nchunk = ((size_t)nraw + rows_per - 1) / rows_per;
+    std::vector<std::atomic<int64_t>> rows_left(nchunk);
+    for (size_t c = 0; c < nchunk; c++) rows_left[c].store((int64_t)std::min<size_t>(rows_per, (size_t)nraw - c * rows_per));
+    std::mutex copy_mu;
+    size_t next_copy = 0;                                        // (under copy_mu) chunks [0, next_copy) have been queued
+    auto chunk_done = [&]() {
+      std::lock_guard<std::mutex> g(copy_mu);
+      D2_HIP(hipSetDevice(device));                              // (a pool thread: the device is a per-thread setting)
+      while (next_copy < nchunk && rows_left[next_copy].load() == 0) {
+        const size_t r0 = next_copy * rows_per, nr = std::min<size_t>(rows_per, (size_t)nraw - r0);
+        D2_HIP(hipMemcpyAsync(D.qual + r0 * LQ, hq.p + r0 * LQ, nr * (size_t)LQ, hipMemcpyHostToDevice, s->side));
+        next_copy++;
+      }
+    };
+    parallel_for((size_t)nraw, grain, [&](size_t lo, size_t hi) {
+      int mx = 0, bad = 0;
+      for (size_t c_lo = lo; c_lo < hi;) {                       // (a piece lies in one chunk; an inline job spans them all)
+        const size_t chunk = c_lo / rows_per, c_hi = std::min(hi, (chunk + 1) * rows_per);
+        for (size_t r = c_lo; r < c_hi; r++) {
           const double *src = quals + r * (size_t)maxlen;
           uint8_t *dst = hq.p + r * (size_t)LQ;
           const int L = s->h_len[r];
-          // the row in one branch-free sweep (it vectorises: the scalar form below was 17 cycles per quality, and the 2 GB of a
-          // 10^6-unique matrix made it the largest piece of the upload) - valid for values in [0, 255.5); a row with anything
-          // else (negative, too large, NaN inside the read) is redone by the exact scalar rule
+          // the row by hostsimd.cpp's branch-free sweep - valid for values in [0, 255.5); a row with anything else (negative,
+          // too large, NaN inside the read) is redone by the exact scalar rule
           int row_mx = 0;
           if (!d2::round_quality_row(src, dst, L, &row_mx)) {
             row_mx = 0;
@@ -451,18 +458,23 @@ void sample_create(dada2hip_sample *s, int32_t nraw, const char *const *seqs, co
           mx = std::max(mx, row_mx);
           memset(dst + L, 0, (size_t)(LQ - L));
         }
-        if (bad) badq.store(1, std::memory_order_relaxed);
-        int cur = qmax.load();
-        while (mx > cur && !qmax.compare_exchange_weak(cur, mx)) {}
-      }, marshal_threads);
-      D2_HIP(hipMemcpyAsync(D.qual + r0 * LQ, hq.p + r0 * LQ, nr * (size_t)LQ, hipMemcpyHostToDevice, s->side));
-    }
+        if (rows_left[chunk].fetch_sub((int64_t)(c_hi - c_lo)) == (int64_t)(c_hi - c_lo)) chunk_done();
+        c_lo = c_hi;
+      }
+      if (bad) badq.store(1, std::memory_order_relaxed);
+      int cur = qmax.load();
+      while (mx > cur && !qmax.compare_exchange_weak(cur, mx)) {}
+    }, marshal_threads);
+    if (next_copy != nchunk) throw RuntimeErr{DADA2HIP_ERR_RUNTIME, "dada2hip: quality upload left a chunk behind"};
+    lap(2);
     D2_HIP(hipStreamSynchronize(s->side));                    // (the pinned buffer goes back to the cache)
+    lap(3);
     if (badq.load()) throw InputError{"Invalid derep$quals matrix. Quality values must be positive integers."};
     s->qmax = qmax.load();
   }
   D2_HIP(hipStreamSynchronize(s->stream));
   D2_HIP(hipGetLastError());
+  lap(4);
   s->ms_upload = ms_since(t0);
 }
 
@@ -637,6 +649,13 @@ struct Run {
   DevBuf<int32_t> d_next;                       // [0] = centre of the speculatively launched next round, -1 = none
   PinBuf<RoundOut> h_rout;                      // the round tail's result block (one D2H per round)
   PinBuf<int32_t> h_big;                        // long mover lists
+  // pinned staging of the final pass (every copy between host and device there is asynchronous for the host)
+  PinBuf<int32_t> f_work, f_cc, f_centres, f_nsubs, f_subqual, f_misc, f_bpairs, f_wgl, f_wnw, f_ph_ji;
+  PinBuf<uint8_t> f_correct, f_pcls;
+  PinBuf<double> f_pval, f_ph_lam;
+  PinBuf<unsigned long long> f_qsum;
+  PinBuf<uint32_t> f_qn;
+  PinBuf<uint16_t> f_bview;
   DevBuf<int32_t> d_pool, d_thresh_one, d_thresh_round;   // zeroed counter pool; k-mer threshold tables
   size_t pool_next = 0;
   static constexpr size_t POOL_INTS = 1 << 18;
@@ -2424,6 +2443,9 @@ void sample_run(dada2hip_sample *s, const double *err, int err_ncol, const dada2
   if (knobs().v2_summary)
     fprintf(stderr, "[run] setup %.2f ms: aligner ring / run cache %.2f  init_run %.2f  alloc_state %.2f  b_init mirror %.2f  v2_alloc %.2f\n", run.st.ms_setup,
             t_sub[0], t_sub[1], t_sub[2], t_sub[3], t_sub[4]);
+  if (knobs().v2_summary)
+    fprintf(stderr, "[run] upload %.2f ms: lengths %.2f  packing %.2f  quality conversion %.2f  wait side stream %.2f  wait main stream %.2f\n",
+            s->ms_upload, s->ms_upload_part[0], s->ms_upload_part[1], s->ms_upload_part[2], s->ms_upload_part[3], s->ms_upload_part[4]);
   const auto t_round0 = clk::now();
   run.compare_round(0, (int)run.bi[0].center, 1.0);   // Rmain.cpp:309-310: no k-mer screen in round 0
   run.st.ms_round0 = ms_since(t_round0);
@@ -2484,63 +2506,96 @@ void sample_run(dada2hip_sample *s, const double *err, int err_ncol, const dada2
   if (fk == NWK_WIDE) wide_fin = opts->band_size > 0 && nw_adw_ok(D, run.ap) && nw_adw_lds_bytes(D, run.ap) <= 150 * 1024;
   if (wide_fin) { coop_fin = false; ensure_adw_scratch(s, run.ap); }
   const size_t per = coop_fin ? (size_t)nw_ad_apw(D, run.ap) : (wide_fin ? (size_t)nw_adw_apw(D, run.ap) : 64);
-  std::vector<int32_t> work, chunk_centre, centre_of_cluster(C);
-  work.reserve((size_t)N + per * (size_t)C);
+  std::vector<int32_t> ph_ji;
+  std::vector<double> ph_lam;
+  // Everything the device reads from or writes to the host in this pass goes through pinned staging of the run (from the
+  // allocation cache): a copy to or from pageable memory holds the calling thread until it has happened, which made the
+  // host wait for the alignments three times over before it could prepare the next piece.  Now the whole pass is queued as one
+  // dependent chain, the host does its share of the assembly while the chain runs, and waits for the chain once.
+  size_t nwork = 0, nchunk = 0;
   uint64_t n_final_local = 0;
+  run.f_centres.alloc((size_t)C);
+  for (int i = 0; i < C; i++) run.f_centres.p[i] = (int32_t)run.bi[i].center;
   if (!shard) {
     // every member of every partition, a partition's members in list order, padded to whole chunks: the member lists ARE the
     // work list (one block copy per partition instead of a push per unique: 10^6 uniques cost 5 ms here)
     size_t tot = 0;
     for (int i = 0; i < C; i++) tot += (run.bi[i].raw.size() + per - 1) / per * per;
-    work.assign(tot, -1);
-    chunk_centre.resize(tot / per);
+    run.f_work.alloc(std::max(tot, per)); run.f_cc.alloc(std::max<size_t>(tot / per, 1));
+    int32_t *work = run.f_work.p, *chunk_centre = run.f_cc.p;
     size_t off = 0;
     for (int i = 0; i < C; i++) {
-      centre_of_cluster[i] = (int32_t)run.bi[i].center;
       const auto &m = run.bi[i].raw;
       static_assert(sizeof(m[0]) == sizeof(int32_t), "member lists are 32-bit");
-      if (!m.empty()) memcpy(work.data() + off, m.data(), m.size() * sizeof(int32_t));
+      if (!m.empty()) memcpy(work + off, m.data(), m.size() * sizeof(int32_t));
       const size_t nch = (m.size() + per - 1) / per;
-      std::fill(chunk_centre.begin() + off / per, chunk_centre.begin() + off / per + nch, (int32_t)run.bi[i].center);
+      std::fill(work + off + m.size(), work + off + nch * per, -1);
+      std::fill(chunk_centre + off / per, chunk_centre + off / per + nch, (int32_t)run.bi[i].center);
       off += nch * per;
       n_final_local += m.size();
     }
-  } else
-  for (int i = 0; i < C; i++) {
-    centre_of_cluster[i] = (int32_t)run.bi[i].center;
-    const auto &m = run.bi[i].raw;
-    size_t kk = 0;
-    for (size_t k = 0; k < m.size(); k++) {
-      if ((int)m[k] < D.r_lo || (int)m[k] >= D.r_hi) continue;   // (sharded run: the members of this rank's block)
-      if (kk++ % per == 0) chunk_centre.push_back((int32_t)run.bi[i].center);
-      work.push_back((int32_t)m[k]);
-      n_final_local++;
+    nwork = tot; nchunk = tot / per;
+  } else {
+    std::vector<int32_t> work, chunk_centre;
+    for (int i = 0; i < C; i++) {
+      const auto &m = run.bi[i].raw;
+      size_t kk = 0;
+      for (size_t k = 0; k < m.size(); k++) {
+        if ((int)m[k] < D.r_lo || (int)m[k] >= D.r_hi) continue;   // (sharded run: the members of this rank's block)
+        if (kk++ % per == 0) chunk_centre.push_back((int32_t)run.bi[i].center);
+        work.push_back((int32_t)m[k]);
+        n_final_local++;
+      }
+      while (work.size() % per) work.push_back(-1);
     }
-    while (work.size() % per) work.push_back(-1);
+    run.f_work.alloc(std::max(work.size(), per)); run.f_cc.alloc(std::max<size_t>(chunk_centre.size(), 1));
+    if (!work.empty()) memcpy(run.f_work.p, work.data(), work.size() * 4);
+    if (!chunk_centre.empty()) memcpy(run.f_cc.p, chunk_centre.data(), chunk_centre.size() * 4);
+    nwork = work.size(); nchunk = chunk_centre.size();
   }
-  if (work.empty()) { work.assign(per, -1); chunk_centre.push_back((int32_t)run.bi[0].center); }
-  s->d_work.alloc(work.size()); s->d_chunk_centre.alloc(chunk_centre.size());
+  if (nwork == 0) { std::fill(run.f_work.p, run.f_work.p + per, -1); run.f_cc.p[0] = (int32_t)run.bi[0].center; nwork = per; nchunk = 1; }
+  s->d_work.alloc(nwork); s->d_chunk_centre.alloc(nchunk);
   s->d_view.alloc((size_t)N * LV);
   s->d_correct.alloc(N);
   s->d_trans.alloc((size_t)16 * err_ncol); s->d_nsubs.alloc(N);
   s->d_qsum.alloc((size_t)C * D.maxlen); s->d_qn.alloc((size_t)C * D.maxlen);
-  D2_HIP(hipMemcpyAsync(s->d_work.p, work.data(), work.size() * 4, hipMemcpyHostToDevice, stq));
-  D2_HIP(hipMemcpyAsync(s->d_chunk_centre.p, chunk_centre.data(), chunk_centre.size() * 4, hipMemcpyHostToDevice, stq));
+  const size_t nq = (size_t)C * D.maxlen, nsq = (size_t)16 * err_ncol;
+  run.f_pval.alloc(N); run.f_correct.alloc(N); run.f_nsubs.alloc(N); run.f_qsum.alloc(nq); run.f_qn.alloc(nq);
+  run.f_subqual.alloc(nsq); run.f_misc.alloc(16); run.f_bview.alloc((size_t)C * LV);
+
+  // the classes of the birth pairs (parent centre vs new centre, known since the rounds ended): on the side stream, in front of
+  // the big launch - nothing in them depends on the final alignments
+  const int nb = C - 1;
+  DevBuf<int32_t> d_bcc, d_braw, d_wgl, d_wnw;
+  DevBuf<uint8_t> d_bcls;
+  if (nb > 0) {
+    run.f_bpairs.alloc(2 * (size_t)nb); run.f_pcls.alloc(nb);
+    int32_t *bcc = run.f_bpairs.p, *braw = run.f_bpairs.p + nb;
+    for (int i = 1; i < C; i++) { bcc[i - 1] = (int32_t)run.bi[run.bi[i].birth_comp.i].center; braw[i - 1] = (int32_t)run.bi[i].center; }
+    d_bcc.alloc(nb); d_braw.alloc(nb); d_bcls.alloc(nb);
+    D2_HIP(hipMemcpyAsync(d_bcc.p, bcc, (size_t)nb * 4, hipMemcpyHostToDevice, s->side));
+    D2_HIP(hipMemcpyAsync(d_braw.p, braw, (size_t)nb * 4, hipMemcpyHostToDevice, s->side));
+    launch_pair_class(D, d_bcc.p, d_braw.p, nb, run.sp, d_bcls.p, s->side);
+    D2_HIP(hipMemcpyAsync(run.f_pcls.p, d_bcls.p, (size_t)nb, hipMemcpyDeviceToHost, s->side));
+  }
+
+  D2_HIP(hipMemcpyAsync(s->d_work.p, run.f_work.p, nwork * 4, hipMemcpyHostToDevice, stq));
+  D2_HIP(hipMemcpyAsync(s->d_chunk_centre.p, run.f_cc.p, nchunk * 4, hipMemcpyHostToDevice, stq));
   if (opts->band_size == 0) {
-    launch_gapless(D, 0, s->d_chunk_centre.p, s->d_work.p, nullptr, (int)work.size(), run.ap, s->d_err.p, s->d_lambda.p,
+    launch_gapless(D, 0, s->d_chunk_centre.p, s->d_work.p, nullptr, (int)nwork, run.ap, s->d_err.p, s->d_lambda.p,
                    s->d_ham.p, s->d_view.p, LV, 0, stq);
     run.st.ngapless += n_final_local;
   } else {
     const int evn_i = run.ev_begin(Run::EV_NW, true, false, /*big=*/true);
     if (coop_fin)
-      launch_nw_ad(D, 0, s->d_chunk_centre.p, s->d_work.p, nullptr, (int)work.size(), nullptr, nullptr, run.ap, s->d_err.p,
+      launch_nw_ad(D, 0, s->d_chunk_centre.p, s->d_work.p, nullptr, (int)nwork, nullptr, nullptr, run.ap, s->d_err.p,
                    s->d_lambda.p, s->d_ham.p, s->d_view.p, LV, 0, nullptr, stq);
     else if (wide_fin)
-      launch_nw_adw(D, 0, s->d_chunk_centre.p, s->d_work.p, nullptr, (int)work.size(), run.ap, s->d_err.p, s->scr_adw.p,
+      launch_nw_adw(D, 0, s->d_chunk_centre.p, s->d_work.p, nullptr, (int)nwork, run.ap, s->d_err.p, s->scr_adw.p,
                     s->scr_adw_wpw, s->scr_adw_waves, s->d_lambda.p, s->d_ham.p, s->d_view.p, LV, 0, stq);
     else {
       ensure_scratch(s, run.ap.band);
-      launch_nw(D, run.wclass, 0, s->d_chunk_centre.p, s->d_work.p, nullptr, (int)work.size(), run.ap, s->d_err.p, s->scr,
+      launch_nw(D, run.wclass, 0, s->d_chunk_centre.p, s->d_work.p, nullptr, (int)nwork, run.ap, s->d_err.p, s->scr,
                 s->d_lambda.p, s->d_ham.p, s->d_view.p, LV, 0, nullptr, 0, nullptr, stq);
     }
     run.ev_end(evn_i);
@@ -2549,107 +2604,143 @@ void sample_run(dada2hip_sample *s, const double *err, int err_ncol, const dada2
   // final per-unique p and the OMEGA_C decision (Rmain.cpp:238-252), on the device
   const int ev_fin = run.ev_begin(Run::EV_FINAL, run.profile_all);
   launch_final_p(run.P, D, opts->omegaC, s->d_correct.p, stq);
-  std::vector<uint8_t> correct(N);
-  R->pval.assign(N, 0.0);
-  D2_HIP(hipMemcpyAsync(R->pval.data(), run.P.p, (size_t)N * 8, hipMemcpyDeviceToHost, stq));
-  D2_HIP(hipMemcpyAsync(correct.data(), s->d_correct.p, (size_t)N, hipMemcpyDeviceToHost, stq));
-  D2_HIP(hipMemsetAsync(s->d_trans.p, 0, (size_t)16 * err_ncol * 4, stq));
-  D2_HIP(hipMemsetAsync(s->d_qsum.p, 0, (size_t)C * D.maxlen * 8, stq));
-  D2_HIP(hipMemsetAsync(s->d_qn.p, 0, (size_t)C * D.maxlen * 4, stq));
-  launch_final_tables(D, s->d_view.p, LV, s->d_work.p, (int)work.size(), run.P.clust_of, run.P.centre_of, s->d_correct.p, err_ncol, 1,
+  D2_HIP(hipMemcpyAsync(run.f_pval.p, run.P.p, (size_t)N * 8, hipMemcpyDeviceToHost, stq));
+  D2_HIP(hipMemcpyAsync(run.f_correct.p, s->d_correct.p, (size_t)N, hipMemcpyDeviceToHost, stq));
+  D2_HIP(hipMemsetAsync(s->d_trans.p, 0, nsq * 4, stq));
+  D2_HIP(hipMemsetAsync(s->d_qsum.p, 0, nq * 8, stq));
+  D2_HIP(hipMemsetAsync(s->d_qn.p, 0, nq * 4, stq));
+  launch_final_tables(D, s->d_view.p, LV, s->d_work.p, (int)nwork, run.P.clust_of, run.P.centre_of, s->d_correct.p, err_ncol, 1,
                       s->d_trans.p, s->d_qsum.p, s->d_qn.p, s->d_nsubs.p, C, stq);
   run.ev_end(ev_fin);
-  std::vector<int32_t> nsubs(N);
-  std::vector<unsigned long long> qsum((size_t)C * D.maxlen);
-  std::vector<uint32_t> qn((size_t)C * D.maxlen);
-  R->subqual.assign((size_t)16 * err_ncol, 0);
-  D2_HIP(hipMemcpyAsync(nsubs.data(), s->d_nsubs.p, (size_t)N * 4, hipMemcpyDeviceToHost, stq));
-  D2_HIP(hipMemcpyAsync(qsum.data(), s->d_qsum.p, qsum.size() * 8, hipMemcpyDeviceToHost, stq));
-  D2_HIP(hipMemcpyAsync(qn.data(), s->d_qn.p, qn.size() * 4, hipMemcpyDeviceToHost, stq));
-  D2_HIP(hipMemcpyAsync(R->subqual.data(), s->d_trans.p, R->subqual.size() * 4, hipMemcpyDeviceToHost, stq));
+  D2_HIP(hipMemcpyAsync(run.f_nsubs.p, s->d_nsubs.p, (size_t)N * 4, hipMemcpyDeviceToHost, stq));
+  D2_HIP(hipMemcpyAsync(run.f_qsum.p, s->d_qsum.p, nq * 8, hipMemcpyDeviceToHost, stq));
+  D2_HIP(hipMemcpyAsync(run.f_qn.p, s->d_qn.p, nq * 4, hipMemcpyDeviceToHost, stq));
+  D2_HIP(hipMemcpyAsync(run.f_subqual.p, s->d_trans.p, nsq * 4, hipMemcpyDeviceToHost, stq));
 
-  // post-hoc partition p-values (error.cpp:101-119): comparisons of partition i against the centres of others
-  std::vector<int32_t> ph_ji;
-  std::vector<double> ph_lam;
-  {
-    std::vector<int32_t> cl_of_centre(N, -1);
-    for (int i = 0; i < C; i++) cl_of_centre[run.bi[i].center] = i;
-    const int cap = std::max(1 << 16, 4 * C * 64);
-    run.d_cl_of_centre.alloc(N); run.d_ph_ji.alloc(2 * (size_t)cap); run.d_ph_lam.alloc(cap); run.d_ph_n.alloc(1);
-    D2_HIP(hipMemcpyAsync(run.d_cl_of_centre.p, cl_of_centre.data(), (size_t)N * 4, hipMemcpyHostToDevice, stq));
-    D2_HIP(hipMemsetAsync(run.d_ph_n.p, 0, 4, stq));
-    auto posthoc = [&](int capv) {
-      if (run.use_v2) launch2_posthoc(run.E2, run.d_cl_of_centre.p, run.d_ph_ji.p, run.d_ph_lam.p, run.d_ph_n.p, capv, stq);
-      else launch_posthoc(run.P, D, run.d_cl_of_centre.p, run.d_ph_ji.p, run.d_ph_lam.p, run.d_ph_n.p, capv, stq);
-    };
-    posthoc(cap);
-    int32_t n = 0;
-    D2_HIP(hipMemcpyAsync(&n, run.d_ph_n.p, 4, hipMemcpyDeviceToHost, stq));
-    D2_HIP(hipStreamSynchronize(stq));
-    if (n > cap) {   // dense centre-vs-centre store: retry with the exact size
-      run.d_ph_ji.alloc(2 * (size_t)n); run.d_ph_lam.alloc(n);
-      D2_HIP(hipMemsetAsync(run.d_ph_n.p, 0, 4, stq));
-      posthoc(n);
-      D2_HIP(hipStreamSynchronize(stq));
-    }
-    ph_ji.resize(2 * (size_t)n); ph_lam.resize(n);
-    if (n) {
-      D2_HIP(hipMemcpy(ph_ji.data(), run.d_ph_ji.p, ph_ji.size() * 4, hipMemcpyDeviceToHost));
-      D2_HIP(hipMemcpy(ph_lam.data(), run.d_ph_lam.p, ph_lam.size() * 8, hipMemcpyDeviceToHost));
-    }
-  }
+  // post-hoc partition p-values (error.cpp:101-119): comparisons of partition i against the centres of others.  The partition
+  // of a centre: -1 everywhere, the C centres scattered by a kernel (no N-entry table filled and copied from the host)
+  const int ph_cap = std::max(1 << 16, 4 * C * 64);
+  run.d_cl_of_centre.alloc(N); run.d_ph_ji.alloc(2 * (size_t)ph_cap); run.d_ph_lam.alloc(ph_cap); run.d_ph_n.alloc(1);
+  s->d_centre_of_cluster.alloc(C);
+  D2_HIP(hipMemsetAsync(run.d_cl_of_centre.p, 0xFF, (size_t)N * 4, stq));
+  D2_HIP(hipMemcpyAsync(s->d_centre_of_cluster.p, run.f_centres.p, (size_t)C * 4, hipMemcpyHostToDevice, stq));
+  launch_scatter_index(s->d_centre_of_cluster.p, C, run.d_cl_of_centre.p, N, stq);
+  D2_HIP(hipMemsetAsync(run.d_ph_n.p, 0, 4, stq));
+  auto posthoc = [&](int capv) {
+    if (run.use_v2) launch2_posthoc(run.E2, run.d_cl_of_centre.p, run.d_ph_ji.p, run.d_ph_lam.p, run.d_ph_n.p, capv, stq);
+    else launch_posthoc(run.P, D, run.d_cl_of_centre.p, run.d_ph_ji.p, run.d_ph_lam.p, run.d_ph_n.p, capv, stq);
+  };
+  posthoc(ph_cap);
+  D2_HIP(hipMemcpyAsync(run.f_misc.p, run.d_ph_n.p, 4, hipMemcpyDeviceToHost, stq));   // (read at the one wait below: the overflow retry)
 
   // birth substitutions (Rmain.cpp:209-215,231-234): parent centre vs new centre, k-mers on, cutoff 1.0.
-  // One pair per wave chunk; the aligned views go to their own plane, one row per pair.
-  std::vector<uint16_t> bview((size_t)C * LV, 0);
-  if (C > 1) {
-    const int nb = C - 1;
-    std::vector<int32_t> bcc(nb), braw(nb);
-    for (int i = 1; i < C; i++) { bcc[i - 1] = (int32_t)run.bi[run.bi[i].birth_comp.i].center; braw[i - 1] = (int32_t)run.bi[i].center; }
-    DevBuf<int32_t> d_bcc, d_braw, d_wgl, d_wnw;
-    DevBuf<uint8_t> d_bcls;
-    d_bcc.alloc(nb); d_braw.alloc(nb); d_bcls.alloc(nb);
-    D2_HIP(hipMemcpyAsync(d_bcc.p, bcc.data(), (size_t)nb * 4, hipMemcpyHostToDevice, stq));
-    D2_HIP(hipMemcpyAsync(d_braw.p, braw.data(), (size_t)nb * 4, hipMemcpyHostToDevice, stq));
-    launch_pair_class(D, d_bcc.p, d_braw.p, nb, run.sp, d_bcls.p, stq);
-    std::vector<uint8_t> pair_cls(nb);
-    D2_HIP(hipMemcpyAsync(pair_cls.data(), d_bcls.p, (size_t)nb, hipMemcpyDeviceToHost, stq));
-    D2_HIP(hipStreamSynchronize(stq));
+  // One pair per wave chunk; the aligned views go to their own plane, one row per pair.  Their work lists are built from the
+  // pair classes (long there: the side stream had only them to do) while the big launch runs, and queued behind the tables.
+  uint16_t *bview = run.f_bview.p;
+  memset(bview, 0, (size_t)C * LV * 2);
+  int n_gl = 0, n_nw = 0;
+  if (nb > 0) {
+    D2_HIP(hipStreamSynchronize(s->side));
+    const uint8_t *pair_cls = run.f_pcls.p;
+    const int32_t *braw = run.f_bpairs.p + nb;
     bool coop_b = coop_fin_ok && !wide_fin;          // one pair per chunk: the cooperative kernels need no 64-wide batch
     if (fk == NWK_LANE) coop_b = false;
     const size_t pern = coop_b ? (size_t)nw_ad_apw(D, run.ap) : (wide_fin ? (size_t)nw_adw_apw(D, run.ap) : 64);
-    std::vector<int32_t> w_gl((size_t)nb * 64, -1), w_nw((size_t)nb * pern, -1);
-    int n_gl = 0, n_nw = 0;
+    const size_t n_wgl = (size_t)nb * 64, n_wnw = (size_t)nb * pern;
+    run.f_wgl.alloc(n_wgl); run.f_wnw.alloc(n_wnw);
+    std::fill(run.f_wgl.p, run.f_wgl.p + n_wgl, -1);
+    std::fill(run.f_wnw.p, run.f_wnw.p + n_wnw, -1);
     for (int k = 0; k < nb; k++) {
-      if (pair_cls[k] == CLS_GAPLESS) { w_gl[(size_t)k * 64] = braw[k]; n_gl++; }
-      else { w_nw[(size_t)k * pern] = braw[k]; n_nw++; }
+      if (pair_cls[k] == CLS_GAPLESS) { run.f_wgl.p[(size_t)k * 64] = braw[k]; n_gl++; }
+      else { run.f_wnw.p[(size_t)k * pern] = braw[k]; n_nw++; }
     }
-    d_wgl.alloc(w_gl.size()); d_wnw.alloc(w_nw.size());
+    d_wgl.alloc(n_wgl); d_wnw.alloc(n_wnw);
     s->d_view_b.alloc((size_t)nb * LV);
-    D2_HIP(hipMemcpyAsync(d_wgl.p, w_gl.data(), w_gl.size() * 4, hipMemcpyHostToDevice, stq));
-    D2_HIP(hipMemcpyAsync(d_wnw.p, w_nw.data(), w_nw.size() * 4, hipMemcpyHostToDevice, stq));
+    D2_HIP(hipMemcpyAsync(d_wgl.p, run.f_wgl.p, n_wgl * 4, hipMemcpyHostToDevice, stq));
+    D2_HIP(hipMemcpyAsync(d_wnw.p, run.f_wnw.p, n_wnw * 4, hipMemcpyHostToDevice, stq));
     D2_HIP(hipMemsetAsync(s->d_view_b.p, 0, (size_t)nb * LV * 2, stq));
-    if (n_gl) launch_gapless(D, 0, d_bcc.p, d_wgl.p, nullptr, (int)w_gl.size(), run.ap, s->d_err.p, s->d_lambda.p, s->d_ham.p,
+    if (n_gl) launch_gapless(D, 0, d_bcc.p, d_wgl.p, nullptr, (int)n_wgl, run.ap, s->d_err.p, s->d_lambda.p, s->d_ham.p,
                              s->d_view_b.p, LV, 1, stq);
     if (n_nw && coop_b)
-      launch_nw_ad(D, 0, d_bcc.p, d_wnw.p, nullptr, (int)w_nw.size(), nullptr, nullptr, run.ap, s->d_err.p, s->d_lambda.p,
+      launch_nw_ad(D, 0, d_bcc.p, d_wnw.p, nullptr, (int)n_wnw, nullptr, nullptr, run.ap, s->d_err.p, s->d_lambda.p,
                    s->d_ham.p, s->d_view_b.p, LV, 1, nullptr, stq);
     else if (n_nw && wide_fin)
-      launch_nw_adw(D, 0, d_bcc.p, d_wnw.p, nullptr, (int)w_nw.size(), run.ap, s->d_err.p, s->scr_adw.p, s->scr_adw_wpw,
+      launch_nw_adw(D, 0, d_bcc.p, d_wnw.p, nullptr, (int)n_wnw, run.ap, s->d_err.p, s->scr_adw.p, s->scr_adw_wpw,
                     s->scr_adw_waves, s->d_lambda.p, s->d_ham.p, s->d_view_b.p, LV, 1, stq);
     else if (n_nw) {
       ensure_scratch(s, run.ap.band);
-      launch_nw(D, run.wclass, 0, d_bcc.p, d_wnw.p, nullptr, (int)w_nw.size(), run.ap, s->d_err.p, s->scr, s->d_lambda.p,
+      launch_nw(D, run.wclass, 0, d_bcc.p, d_wnw.p, nullptr, (int)n_wnw, run.ap, s->d_err.p, s->scr, s->d_lambda.p,
                 s->d_ham.p, s->d_view_b.p, LV, 1, nullptr, 0, nullptr, stq);
     }
-    D2_HIP(hipMemcpyAsync(&bview[(size_t)LV], s->d_view_b.p, (size_t)nb * LV * 2, hipMemcpyDeviceToHost, stq));
-    D2_HIP(hipStreamSynchronize(stq));
+    D2_HIP(hipMemcpyAsync(bview + (size_t)LV, s->d_view_b.p, (size_t)nb * LV * 2, hipMemcpyDeviceToHost, stq));
     if (!shard || shard->rank == 0) {                       // (every rank aligns the few birth pairs; counted once)
       run.st.ngapless += (uint64_t)n_gl;
       run.st.nnw += (uint64_t)n_nw;
     }
   }
-  D2_HIP(hipStreamSynchronize(stq));
+
+  // ---- the host's share while the chain runs: the result's own vectors (first touch of 12 MB at 10^6 uniques) and the
+  // representative of every partition - b_make_clustering_df (error.cpp:19-34) takes the member with the most reads, the FIRST
+  // such in list order = the lowest slot_of.  (reads, slot) orders the members of a partition totally, so per-piece maxima on
+  // the pool merged in piece order give what one pass over the uniques gave.
+  R->pval.assign(N, 0.0);
+  R->map.assign(N, DADA2HIP_NA_INTEGER);   // Rmain.cpp:268-279
+  R->subqual.assign(nsq, 0);
+  const size_t asm_pieces = std::min<size_t>(256, std::max<size_t>(1, ((size_t)1 << 20) / (size_t)C));
+  const size_t asm_grain = std::max<size_t>(4096, ((size_t)N + asm_pieces - 1) / asm_pieces);
+  const size_t asm_T = ((size_t)N + asm_grain - 1) / asm_grain;
+  // (lo / asm_grain names a piece's own row of the partial arrays: HostPool hands out pieces that start on multiples of the grain,
+  //  or the whole range in one inline call - a pool that cut pieces elsewhere would make two pieces share a row)
+  std::vector<uint32_t> max_reads(C, 0);
+  std::vector<int32_t> max_raw(C, -1), max_slot(C, 0);
+  {
+    std::vector<uint32_t> p_reads(asm_T * C, 0);
+    std::vector<int32_t> p_raw(asm_T * C, -1), p_slot(asm_T * C, 0);
+    parallel_for((size_t)N, asm_grain, [&](size_t lo, size_t hi) {
+      const size_t t = lo / asm_grain;
+      uint32_t *mr = p_reads.data() + t * C;
+      int32_t *mw = p_raw.data() + t * C, *ms = p_slot.data() + t * C;
+      for (size_t r = lo; r < hi; r++) {
+        const int i = run.clust_of[r];
+        const uint32_t rd = s->h_reads[r];
+        if (rd > mr[i] || (rd == mr[i] && mw[i] >= 0 && run.slot_of[r] < ms[i])) { mr[i] = rd; mw[i] = (int32_t)r; ms[i] = run.slot_of[r]; }
+      }
+    });
+    for (size_t t = 0; t < asm_T; t++)
+      for (int i = 0; i < C; i++) {
+        const size_t k = t * C + i;
+        if (p_raw[k] < 0) continue;
+        if (p_reads[k] > max_reads[i] || (p_reads[k] == max_reads[i] && max_raw[i] >= 0 && p_slot[k] < max_slot[i])) {
+          max_reads[i] = p_reads[k]; max_raw[i] = p_raw[k]; max_slot[i] = p_slot[k];
+        }
+      }
+  }
+
+  // the one wait for the chain (before it only the side stream's pair classes were waited for, done long since; behind it only
+  // the post-hoc lists are fetched, whose number arrives with it)
+  sync_spin(stq);
+  {
+    int32_t n = run.f_misc.p[0];
+    if (n > ph_cap) {   // dense centre-vs-centre store: retry with the exact size
+      run.d_ph_ji.alloc(2 * (size_t)n); run.d_ph_lam.alloc(n);
+      D2_HIP(hipMemsetAsync(run.d_ph_n.p, 0, 4, stq));
+      posthoc(n);
+      D2_HIP(hipStreamSynchronize(stq));
+    }
+    if (n) {   // their number is known only now: fetched behind the wait, through pinned staging like everything else
+      run.f_ph_ji.alloc(2 * (size_t)n); run.f_ph_lam.alloc(n);
+      D2_HIP(hipMemcpyAsync(run.f_ph_ji.p, run.d_ph_ji.p, 2 * (size_t)n * 4, hipMemcpyDeviceToHost, stq));
+      D2_HIP(hipMemcpyAsync(run.f_ph_lam.p, run.d_ph_lam.p, (size_t)n * 8, hipMemcpyDeviceToHost, stq));
+      D2_HIP(hipStreamSynchronize(stq));
+      ph_ji.assign(run.f_ph_ji.p, run.f_ph_ji.p + 2 * (size_t)n); ph_lam.assign(run.f_ph_lam.p, run.f_ph_lam.p + n);
+    }
+  }
+  uint8_t *correct = run.f_correct.p;
+  int32_t *nsubs = run.f_nsubs.p;
+  unsigned long long *qsum = run.f_qsum.p;
+  uint32_t *qn = run.f_qn.p;
+  parallel_for((size_t)N, 65536, [&](size_t lo, size_t hi) { memcpy(R->pval.data() + lo, run.f_pval.p + lo, (hi - lo) * 8); });
+  memcpy(R->subqual.data(), run.f_subqual.p, nsq * 4);
   D2_HIP(hipGetLastError());
   {   // error flag + run totals of the screen counters
     int32_t ef = 0;
@@ -2722,19 +2813,19 @@ void sample_run(dada2hip_sample *s, const double *err, int err_ncol, const dada2
       }
     };
     gather_block(R->pval.data(), 8);
-    gather_block(correct.data(), 1);
-    gather_block(nsubs.data(), 4);
+    gather_block(correct, 1);
+    gather_block(nsubs, 4);
     {
-      std::vector<int64_t> v(R->subqual.size() + qsum.size() + qn.size());
+      std::vector<int64_t> v(R->subqual.size() + 2 * nq);
       size_t o = 0;
       for (int32_t x : R->subqual) v[o++] = x;
-      for (unsigned long long x : qsum) v[o++] = (int64_t)x;
-      for (uint32_t x : qn) v[o++] = x;
+      for (size_t k = 0; k < nq; k++) v[o++] = (int64_t)qsum[k];
+      for (size_t k = 0; k < nq; k++) v[o++] = qn[k];
       run.sh_allreduce(v);
       o = 0;
       for (auto &x : R->subqual) x = (int32_t)v[o++];          // (int32 wrap-around as R's integer matrix, error.cpp:152-167)
-      for (auto &x : qsum) x = (unsigned long long)v[o++];
-      for (auto &x : qn) x = (uint32_t)v[o++];
+      for (size_t k = 0; k < nq; k++) qsum[k] = (unsigned long long)v[o++];
+      for (size_t k = 0; k < nq; k++) qn[k] = (uint32_t)v[o++];
     }
     {   // post-hoc comparisons (partition of a centre, partition compared, lambda) found in each block's store
       struct Ph { int32_t j, i; double lam; };
@@ -2766,28 +2857,33 @@ void sample_run(dada2hip_sample *s, const double *err, int err_ncol, const dada2
   R->abundance.assign(C, 0); R->n0.assign(C, 0); R->n1.assign(C, 0); R->nunq.assign(C, 0);
   R->birth_from.assign(C, 0); R->birth_ham.assign(C, 0); R->center.assign(C, 0);
   R->clust_pval.assign(C, 0); R->birth_pval.assign(C, 0); R->birth_fold.assign(C, 0); R->birth_qave.assign(C, 0);
-  // b_make_clustering_df (error.cpp:9-127).  The sums over a partition's members are integer sums and the representative
-  // sequence is the member with the most reads, the FIRST such in list order (error.cpp:19-34): one streaming pass over the
-  // uniques in index order with the host mirror's partition / slot of each (the per-partition member loops were 10^6 random
-  // reads into three arrays) gives the same values
-  R->map.assign(N, DADA2HIP_NA_INTEGER);   // Rmain.cpp:268-279
+  // b_make_clustering_df (error.cpp:9-127).  The sums over a partition's members are integer sums (modulo 2^32 in any order):
+  // per-piece partial sums on the pool, added up in piece order; map is written in place.  The representatives were found
+  // while the device was still at work (above).
   {
-    std::vector<uint32_t> max_reads(C, 0);
-    std::vector<int32_t> max_raw(C, -1), max_slot(C, 0);
-    for (int r = 0; r < N; r++) {
-      const int i = run.clust_of[r];
-      const uint32_t rd = s->h_reads[r];
-      if (rd > max_reads[i] || (rd == max_reads[i] && max_raw[i] >= 0 && run.slot_of[r] < max_slot[i])) {
-        max_reads[i] = rd; max_raw[i] = r; max_slot[i] = run.slot_of[r];
+    std::vector<uint32_t> part(asm_T * (size_t)C * 4, 0);    // abundance, nunq, n0, n1 of each partition, per piece
+    parallel_for((size_t)N, asm_grain, [&](size_t lo, size_t hi) {
+      uint32_t *a = part.data() + (lo / asm_grain) * (size_t)C * 4;
+      for (size_t r = lo; r < hi; r++) {
+        if (!correct[r]) continue;
+        const int i = run.clust_of[r];
+        const uint32_t rd = s->h_reads[r];
+        R->map[r] = i + 1;
+        a[4 * i] += rd;
+        a[4 * i + 1]++;
+        if (nsubs[r] == 0) a[4 * i + 2] += rd;
+        if (nsubs[r] == 1) a[4 * i + 3] += rd;
       }
-      if (!correct[r]) continue;
-      R->map[r] = i + 1;
-      R->abundance[i] += (int32_t)rd;
-      R->nunq[i]++;
-      if (nsubs[r] == 0) R->n0[i] += (int32_t)rd;
-      if (nsubs[r] == 1) R->n1[i] += (int32_t)rd;
+    });
+    for (int i = 0; i < C; i++) {
+      uint32_t ab = 0, nu = 0, z0 = 0, z1 = 0;
+      for (size_t t = 0; t < asm_T; t++) {
+        const uint32_t *a = part.data() + (t * C + i) * 4;
+        ab += a[0]; nu += a[1]; z0 += a[2]; z1 += a[3];
+      }
+      R->abundance[i] = (int32_t)ab; R->nunq[i] = (int32_t)nu; R->n0[i] = (int32_t)z0; R->n1[i] = (int32_t)z1;
+      R->sequence[i] = max_raw[i] >= 0 ? seq_string(s, max_raw[i]) : std::string("");
     }
-    for (int i = 0; i < C; i++) R->sequence[i] = max_raw[i] >= 0 ? seq_string(s, max_raw[i]) : std::string("");
   }
   for (int i = 0; i < C; i++) {
     const Bi &b = run.bi[i];

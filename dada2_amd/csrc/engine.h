@@ -125,11 +125,16 @@ struct BudParams {
   int32_t min_hamming, min_abund;
 };
 
-// (uint8) round(x) of one quality row, branch-free (hostsimd.cpp: plain C++ with an AVX2 clone); false = redo the row by the scalar rule
+// hostsimd.cpp (plain C++: a scalar form and an explicit AVX2 form of each, chosen once at load).
+// (uint8) round(x) of the first L doubles of a quality row, *mx_out = the row's maximum; false = redo the row by the exact scalar rule
 bool round_quality_row(const double *src, uint8_t *dst, int L, int *mx_out);
+// the first len characters of q as W2 words of 2-bit codes (padding words zero); non-zero = a byte other than A C G T among them
+uint32_t pack_row_2bit(const char *q, int len, uint32_t *row, int W2);
 
 void launch_fill_f64(double *d_p, size_t n, double v, hipStream_t st);
 void launch_fill_null(int n, const uint8_t *d_cls, double *d_lam, uint32_t *d_ham, hipStream_t st);
+// d_out[d_key[i]] = i, i < n (keys outside [0, n_out) are left out); the caller presets d_out
+void launch_scatter_index(const int32_t *d_key, int n, int32_t *d_out, int n_out, hipStream_t st);
 void launch_store(const PartState &P, const SampleDev &S, int ci, int centre, double total_reads, const double *d_lam,
                   const uint32_t *d_ham, const int32_t *d_round_counters, const uint8_t *d_cls, int32_t *d_zero2, hipStream_t st);
 // The store filter of a round (ci >= 1) rides in front of the round's first shuffle: pass its arguments here.

@@ -70,12 +70,17 @@ class HostPool {
   HostPool() {
     int n = (int)std::thread::hardware_concurrency();
     if (n <= 0) n = 1;
-    if (n > 64) n = 64;                                  // memory-bound copies: 16 / 32 / 64 threads = 55 / 34 / 25 ms for the 1M-unique upload (profiles/r02q_bench_cfg3_threads*.json)
+    // At most 64.  With the marshalling loops in AVX2 (hostsimd.cpp) the headline call takes 132.9-142.1 / 135.0-140.9 / 134.9-138.4 ms
+    // on 16 / 32 / 64 threads, three runs each on one box: inside the spread, so the width stayed; its upload alone 17.2-18.5 /
+    // 14.3-18.1 / 12.7-14.9 ms (profiles/r12e_host_threads.txt).  On the scalar loops it was 55 / 34 / 25 ms (r02q).
+    if (n > 64) n = 64;
     {
       // A container's CPU quota (cgroup v2 cpu.max: "<quota us> <period us>", "max" = none) is invisible to hardware_concurrency():
-      // the GPU boxes show 256 cores and allow sixteen CPUs' worth per 100 ms.  The marshalling is a burst (64 threads x 25 ms =
-      // one whole period's quota at 16 CPUs, measured best there: profiles/r10s_*), so the pool may be four times the quota
-      // wide and no wider - a 4-CPU container gets 16 threads instead of 64 that the kernel would park most of the time.
+      // the GPU boxes show 256 cores and allow sixteen CPUs' worth per 100 ms.  The marshalling is a burst (64 threads x 15 ms = 0.96 CPU-seconds, three
+      // fifths of one period's quota at 16 CPUs; x 25 ms = all of it on the scalar loops, profiles/r10s_*), so the pool may be four
+      // times the quota wide and no wider - a 4-CPU container gets 16 threads instead of 64 that the kernel would park most of the
+      // time.  (Back to back in a stand-alone loop, 64 threads in that quota read memory slower than 32: 359 against 577 GB/s,
+      // profiles/r12a_host_marshal.txt.  Inside a call, one burst per 135 ms, 64 gave the shortest upload.)
       if (FILE *fp = fopen("/sys/fs/cgroup/cpu.max", "r")) {
         char q[32] = "";
         long long period = 0;

@@ -2607,6 +2607,19 @@ void launch_fill_null(int n, const uint8_t *d_cls, double *d_lam, uint32_t *d_ha
   hipLaunchKernelGGL(k_fill_null, dim3((n + 255) / 256), dim3(256), 0, st, n, d_cls, d_lam, d_ham);
 }
 
+// out[key[i]] = i for the n keys (the final pass's partition-of-a-centre table: the caller has set the N entries to -1, and the
+// few hundred centres are scattered here instead of an N-entry table being filled and copied from the host)
+__global__ void k_scatter_index(const int32_t *__restrict__ key, int n, int32_t *__restrict__ out, int n_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t k = key[i];
+  if ((uint32_t)k < (uint32_t)n_out) out[k] = i;
+}
+void launch_scatter_index(const int32_t *d_key, int n, int32_t *d_out, int n_out, hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_scatter_index, dim3((n + 255) / 256), dim3(256), 0, st, d_key, n, d_out, n_out);
+}
+
 void launch_store(const PartState &P, const SampleDev &S, int ci, int centre, double total_reads, const double *d_lam,
                   const uint32_t *d_ham, const int32_t *d_round_counters, const uint8_t *d_cls, int32_t *d_zero2, hipStream_t st) {
   int grid = std::min((S.N + 255) / 256, 2048);
