@@ -119,7 +119,13 @@ EXPORTS = [
     "dada2hip_merge_pairs", "dada2hip_mergers_nrow", "dada2hip_mergers_sequence", "dada2hip_mergers_abundance",
     "dada2hip_mergers_forward", "dada2hip_mergers_reverse", "dada2hip_mergers_nmatch", "dada2hip_mergers_nmismatch",
     "dada2hip_mergers_nindel", "dada2hip_mergers_prefer", "dada2hip_mergers_accept", "dada2hip_mergers_free",
+    "dada2hip_collapse_nomismatch", "dada2hip_collapse_pairs", "dada2hip_nweval",
 ]
+
+COLLAPSE_NSTATS = 16   # DADA2HIP_COLLAPSE_NSTATS
+# the int64 words of dada2hip_collapse_nomismatch's stats, in order (the *_us entries are host wall time in microseconds)
+COLLAPSE_STATS = ("columns_dedup", "candidate_pairs", "pairs_scanned", "pairs_screened_out", "pairs_bound_rejected", "pairs_aligned",
+                  "aligned_ham0", "batches", "join_us", "scan_us", "align_us", "resolve_us", "total_us")
 
 
 class CSampleInput(C.Structure):
@@ -257,6 +263,9 @@ def lib():
         f.restype = C.POINTER(C.c_int32)
     L.dada2hip_mergers_free.argtypes = [vp]
     L.dada2hip_mergers_free.restype = None
+    L.dada2hip_collapse_nomismatch.argtypes = [ip, ip, vp, C.POINTER(cp), ip, ip, ip, ip, ip, ip, ip, vp, vp, cp, C.c_size_t]
+    L.dada2hip_collapse_pairs.argtypes = [ip, C.POINTER(cp), C.POINTER(cp), ip, ip, ip, ip, vp, cp, C.c_size_t]
+    L.dada2hip_nweval.argtypes = [ip, C.POINTER(cp), C.POINTER(cp), ip, ip, ip, ip, ip, ip, ip, ip, vp, cp, C.c_size_t]
     L.dada2hip_trim_cache.argtypes = []
     L.dada2hip_trim_cache.restype = None
     _lib = L

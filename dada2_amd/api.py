@@ -4,7 +4,8 @@
   argument meaning, same six outputs, errors raised with the reference's messages.
 * ``Sample``             — the same call split into "make the uniques resident in HBM" and
   "run with this error matrix", which is what the selfConsist loop of R/dada.R:256-405 needs.
-* ``nwalign`` / ``nwvec`` — R/misc.R:179 ``nwalign()`` -> C_nwalign / C_nwvec.
+* ``nwalign`` / ``nwvec`` — R/misc.R:179 ``nwalign()`` -> C_nwalign / C_nwvec; ``nweval`` / ``nwhamming`` (R/misc.R:216-225).
+* ``make_sequence_table`` / ``collapse_no_mismatch`` — R/multiSample.R:31-55, :104-160.
 * ``dada(...)``          — the per-sample loop + selfConsist loop of R/dada.R:144-487, reduced
   to what the hot path needs (single process; ``dada2_amd.multi`` shards samples over GPUs).
 
@@ -465,6 +466,156 @@ def merge_pairs(dadaF: DadaResult, derepF: Derep, dadaR: DadaResult, derepR: Der
     finally:
         L.dada2hip_mergers_free(h)
     return rows if return_rejects else [r for r in rows if r["accept"]]
+
+
+def _charpp(strs):
+    return (C.c_char_p * max(len(strs), 1))(*[s.encode("ascii") for s in strs])
+
+
+def _vectorize(s1, s2):
+    """R's Vectorize over the two sequence arguments: scalars are accepted, a scalar is recycled against a list."""
+    scalar = isinstance(s1, str) and isinstance(s2, str)
+    a = [s1] if isinstance(s1, str) else list(s1)
+    b = [s2] if isinstance(s2, str) else list(s2)
+    if len(a) != len(b):
+        if len(a) == 1:
+            a = a * len(b)
+        elif len(b) == 1:
+            b = b * len(a)
+        else:
+            raise ValueError("Character vectors to be aligned must be of equal length.")
+    return a, b, scalar
+
+
+def nweval(s1, s2, match=5, mismatch=-4, gap=-8, homo_gap=None, band=-1, endsfree=True, vec=False, device: int = 0):
+    """nweval (R/misc.R:222-225): C_eval_pair of nwalign(s1, s2, ...) - int32 [n, 3] = match, mismatch, indel, end gaps not
+    counted (one row of three for two scalars).  ``vec`` chooses C_nwvec over C_nwalign as in nwalign (R/misc.R:179)."""
+    a, b, scalar = _vectorize(s1, s2)
+    n = len(a)
+    out = np.zeros((n, 3), dtype=np.int32)
+    eb = C.create_string_buffer(_EB)
+    _lib.check(_lib.lib().dada2hip_nweval(n, _charpp(a), _charpp(b), match, mismatch, gap, gap if homo_gap is None else homo_gap,
+                                          int(band), int(endsfree), int(bool(vec)), device, out.ctypes.data, eb, _EB), eb)
+    return out[0] if scalar else out
+
+
+def nwhamming(s1, s2, **kw):
+    """nwhamming (R/misc.R:216-220): mismatches + indels of the alignment, end gaps excluded; an int for two scalars."""
+    ev = nweval(s1, s2, **kw)
+    return int(ev[1] + ev[2]) if ev.ndim == 1 else (ev[:, 1] + ev[:, 2]).astype(np.int32)
+
+
+def collapse_pairs(queries, refs, min_overlap=20, match=5, mismatch=-4, device: int = 0):
+    """What collapse_no_mismatch's scan kernel computes per (query, ref) pair: int32 [n, 4] = screen (bit 0: the first
+    ``min_overlap`` bases of the query occur in the ref, bit 1: the reverse), G (best score of a gapless diagonal), m_max (longest
+    diagonal without a mismatch), decision (0 screened out, 1 rejected by G > match * m_max, 2 needs the alignment)."""
+    n = len(queries)
+    if n != len(refs):
+        raise ValueError("queries and refs must have the same length")
+    out = np.zeros((n, 4), dtype=np.int32)
+    eb = C.create_string_buffer(_EB)
+    _lib.check(_lib.lib().dada2hip_collapse_pairs(n, _charpp(queries), _charpp(refs), int(min_overlap), match, mismatch, device,
+                                                  out.ctypes.data, eb, _EB), eb)
+    return out
+
+
+def _sample_uniques(sample):
+    """getUniques (R/misc.R:33-62) of one sample -> [(sequence, abundance)]: duplicates summed and then, as tapply leaves them,
+    in ascending byte order of the sequences (:53-56)."""
+    if isinstance(sample, DadaResult):
+        pairs = list(zip(sample.clustering["sequence"], sample.clustering["abundance"]))
+    elif isinstance(sample, Derep):
+        pairs = list(zip(sample.seqs, sample.abundances))
+    elif isinstance(sample, dict):
+        pairs = list(sample.items())
+    elif isinstance(sample, (list, tuple)) and all(isinstance(r, dict) and "sequence" in r and "abundance" in r for r in sample):
+        pairs = [(r["sequence"], r["abundance"]) for r in sample if r.get("accept", True)]   # merge_pairs rows: the accepted ones
+    else:
+        raise ValueError("Unrecognized format: Requires a DadaResult, a Derep, a {sequence: abundance} mapping or merge_pairs rows.")
+    pairs = [(str(s), int(a)) for s, a in pairs]
+    if len({s for s, _ in pairs}) == len(pairs):
+        return pairs
+    summed = {}
+    for s, a in pairs:
+        summed[s] = summed.get(s, 0) + a
+    return [(s, summed[s]) for s in sorted(summed, key=lambda x: x.encode("ascii"))]
+
+
+def _order_columns(mat, order_by):
+    """order(colSums(.), decreasing=TRUE) / order(colSums(. > 0), ...) (R/multiSample.R:46-52, :148-154): a stable order."""
+    if order_by is None:
+        return np.arange(mat.shape[1])
+    if order_by == "abundance":
+        key = mat.sum(axis=0, dtype=np.int64)
+    elif order_by == "nsamples":
+        key = (mat > 0).sum(axis=0)
+    else:
+        raise ValueError('order_by must be "abundance", "nsamples" or None')
+    return np.argsort(-key, kind="stable")
+
+
+def make_sequence_table(samples, order_by="abundance"):
+    """makeSequenceTable (R/multiSample.R:31-55): (mat int32 [samples, sequences], seqs).  ``samples``: a list (or one) of
+    DadaResult, Derep, {sequence: abundance} mappings or merge_pairs row lists.  Columns in order of first appearance across the
+    samples, then stably ordered by ``order_by`` ("abundance", "nsamples" or None)."""
+    if isinstance(samples, (DadaResult, Derep, dict)) or (isinstance(samples, list) and samples and isinstance(samples[0], dict)
+                                                            and "sequence" in samples[0]):
+        samples = [samples]
+    if not isinstance(samples, (list, tuple)):
+        raise ValueError("Requires a list of samples.")
+    unqs = [_sample_uniques(s) for s in samples]
+    col = {}
+    for u in unqs:
+        for s, _ in u:
+            col.setdefault(s, len(col))
+    mat = np.zeros((len(unqs), len(col)), dtype=np.int64)
+    for i, u in enumerate(unqs):
+        for s, a in u:
+            mat[i, col[s]] = a
+    if mat.size and mat.max() > np.iinfo(np.int32).max:
+        raise _lib.Dada2HipError(1, "dada2hip: an abundance of the sequence table exceeds the integer range.")
+    mat = mat.astype(np.int32)
+    seqs = list(col)
+    o = _order_columns(mat, order_by)
+    return np.ascontiguousarray(mat[:, o]), [seqs[int(k)] for k in o]
+
+
+def collapse_no_mismatch(mat, seqs, min_overlap=20, order_by="abundance", identical_only=False, vec=True, band=-1, verbose=False,
+                         device: int = 0, match=5, mismatch=-4, gap=-8, stats: dict = None):
+    """collapseNoMismatch (R/multiSample.R:104-160) through dada2hip_collapse_nomismatch: ``mat`` is the [samples, sequences] table,
+    ``seqs`` its column names; returns (mat, seqs) of the collapsed table.  ``vec`` is accepted for signature parity: both values
+    run the same device aligner, which follows nwalign_endsfree.  The library decides which column each
+    column is added to; the sums, the ``order_by`` ordering and the reference's final, unconditional ordering by total abundance
+    (:156, stable - so "nsamples" only breaks abundance ties) are done here.  With ``identical_only`` the de-duplicated table comes
+    back in input order (:115).  ``stats`` (a dict) receives the library's counters (_lib.COLLAPSE_STATS)."""
+    del vec
+    m = np.asarray(mat)
+    if m.ndim != 2 or m.shape[1] != len(seqs):
+        raise ValueError("The sequence table must have one column per sequence.")
+    if m.size and (m.max() > np.iinfo(np.int32).max or m.min() < np.iinfo(np.int32).min):
+        raise _lib.Dada2HipError(1, "dada2hip: an abundance of the sequence table exceeds the integer range.")
+    mf = np.asfortranarray(m.astype(np.int32))
+    nrow, ncol = mf.shape
+    into = np.zeros(ncol, dtype=np.int32)
+    st = np.zeros(_lib.COLLAPSE_NSTATS, dtype=np.int64)
+    eb = C.create_string_buffer(_EB)
+    _lib.check(_lib.lib().dada2hip_collapse_nomismatch(nrow, ncol, mf.ctypes.data, _charpp(seqs), int(min_overlap), int(bool(identical_only)),
+                                                       int(band), match, mismatch, gap, device, into.ctypes.data, st.ctypes.data, eb, _EB), eb)
+    if stats is not None:
+        stats.update({k: int(st[i]) for i, k in enumerate(_lib.COLLAPSE_STATS)})
+        stats["into"] = into.copy()
+    out = np.zeros((nrow, ncol), dtype=np.int64)
+    np.add.at(out, (slice(None), into), mf.astype(np.int64))
+    kept = np.flatnonzero(into == np.arange(ncol))               # input order, modulo the removed columns (:145)
+    out = out[:, kept].astype(np.int32)
+    names = [seqs[int(k)] for k in kept]
+    if not identical_only:
+        for ob in (order_by, "abundance"):
+            o = _order_columns(out, ob)
+            out, names = out[:, o], [names[int(k)] for k in o]
+        if verbose:
+            print("Output %d collapsed sequences out of %d input sequences." % (len(names), int(st[0])))
+    return np.ascontiguousarray(out), names
 
 
 def calc_pA_device(reads, E, prior, device: int = 0):

@@ -3556,6 +3556,9 @@ int dada2hip_nwalign(const char *s1, const char *s2, int32_t match, int32_t mism
   return nwvec_any(1, a, b, match, mismatch, gap_p, homo_gap_p, band, endsfree, device, o, errbuf, errlen);
 }
 
+// ---- the sequence-table stage: collapseNoMismatch, nweval (R/multiSample.R:104-160, R/misc.R:216-225) ----
+#include "collapse_host.h"
+
 // ---- result getters ------------------------------------------------------------------------------
 int32_t dada2hip_result_nclust(const dada2hip_result *r) { return r->nclust; }
 int32_t dada2hip_result_nraw(const dada2hip_result *r) { return r->nraw; }

@@ -568,6 +568,12 @@ void launch3_tail(const Eng2 &E, int grid, bool first, int ordinal, uint32_t ini
 void launch_bimera_lr(const SampleDev &S, const int32_t *d_chunk_centre, const int32_t *d_work, int nwork, const uint8_t *d_moves,
                       int stride, const int32_t *d_nmoves, int allow_one_off, int max_shift, int32_t *d_out, hipStream_t st);
 
+// collapseNoMismatch (collapse.inc.hip): which prefix keys occur in rows [row0, row0 + nrows) (d_bits[nrows][KW], preset to 0), and
+// {screen, G, m_max, decision} of each (query, ref) pair of rows
+void launch_collapse_join(const SampleDev &S, int row0, int nrows, const unsigned long long *d_keys, const int32_t *d_groups,
+                          int ngroups, int KW, uint32_t *d_bits, hipStream_t st);
+void launch_collapse_scan(const SampleDev &S, const int2 *d_pairs, int npairs, int min_overlap, int match, int mismatch, int use_bound,
+                          int4 *d_out, hipStream_t st);
 void launch_calc_pA(int n, const int32_t *d_reads, const double *d_E, const uint8_t *d_prior, double *d_out,
                     hipStream_t st);
 

@@ -2892,6 +2892,8 @@ void launch_bimera_lr(const SampleDev &S, const int32_t *d_chunk_centre, const i
                      d_nmoves, allow_one_off, max_shift, d_out);
 }
 
+#include "collapse.inc.hip"   // collapseNoMismatch: the prefix-key join and the diagonal scan
+
 #include "rounds2.inc.hip"   // (the persistent round tail, rounds3.inc.hip, is the translation unit tail.hip)
 
 }  // namespace d2

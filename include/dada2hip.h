@@ -17,6 +17,8 @@
  *   dada2hip_is_bimera      <- C_is_bimera()       src/chimera.cpp:18-59     (`_dada2_C_is_bimera`; R/chimeras.R:44)
  *   dada2hip_merge_pairs    <- mergePairs()        R/paired.R:92-201 on C_nwalign / C_eval_pair / C_pair_consensus
  *                                                   (src/evaluate.cpp:18-62, :73-114, :124-174)
+ *   dada2hip_collapse_nomismatch <- collapseNoMismatch()  R/multiSample.R:104-160 (grepl screen + nwhamming per pair)
+ *   dada2hip_nweval         <- nweval() / nwhamming()  R/misc.R:216-225
  *   dada2hip_derep_*        <- derepFastq() / qtables2()  R/sequenceIO.R:45-124, :150-183 (host-side C++, zlib)
  *
  * Conventions: plain C, no exceptions cross the boundary.  Every call returns 0 on success or a
@@ -40,6 +42,9 @@
  *   DADA2HIP_WAIT=block, DADA2HIP_WAIT_TIMEOUT_S=<s>   sleep instead of spin while waiting; bound of every device wait
  *   DADA2HIP_HOST_THREADS=<n>, DADA2HIP_ALLOC_CACHE=0, DADA2HIP_ALLOC_CACHE_GB=<n>   marshalling pool, allocation cache
  *   DADA2HIP_DEREP_INFLATE=zlib        dada2hip_derep_fastq: .gz files through zlib's streaming inflate even where libdeflate is installed
+ *   DADA2HIP_COLLAPSE_BATCH=<n>        dada2hip_collapse_nomismatch: queries per batch (default 0 = automatic)
+ *   DADA2HIP_COLLAPSE_SCAN=0           ... every screened pair is aligned (the bound of the diagonal scan is not used)
+ *   DADA2HIP_COLLAPSE_JOIN=0           ... every (query, ref) pair is scanned (no prefix-key join)
  *   DADA2HIP_PROFILE=1, DADA2HIP_V2_SUMMARY, DADA2HIP_V2_DEBUG   per-launch device times in the stats; traces on stderr
  * Test / tuning knobs (sizes of rings and grids, forced growth paths, injected failures) are listed with their meaning in
  * knobs.h and DESIGN.md §10b; they are not part of the interface.
@@ -350,6 +355,41 @@ const int32_t *dada2hip_mergers_nindel(const dada2hip_mergers *m);
 const int32_t *dada2hip_mergers_prefer(const dada2hip_mergers *m);
 const int32_t *dada2hip_mergers_accept(const dada2hip_mergers *m);
 void dada2hip_mergers_free(dada2hip_mergers *m);
+
+/* ---- the sequence-table stage: collapseNoMismatch, nweval / nwhamming ---------------------------------------------------
+ * dada2hip_collapse_nomismatch == the decisions of collapseNoMismatch(seqtab, minOverlap, identicalOnly = identical_only,
+ * band = band) (R/multiSample.R:104-160).  mat is the nrow (samples) x ncol (sequences) integer table, column-major as R holds
+ * it, seqs its column names.  into[ncol] receives, per input column, the 0-BASED input column its counts end up in: the column
+ * itself when it is kept, else the kept column it was added to (a duplicate name goes where its first occurrence goes, so
+ * into[into[i]] == into[i]).  The sums, the removal of the other columns and the two column orders (orderBy, then total
+ * abundance) are the caller's, from `into`.  identical_only != 0 folds duplicate names only (no device work).
+ * Otherwise the columns are processed by decreasing total abundance (stable) in batches; per batch the device decides, for
+ * every (query, kept-or-earlier-in-the-batch ref) pair that can pass the reference's prefix screen, whether it passes it and
+ * whether its gapless diagonals already rule out an alignment without mismatch or internal indel (collapse.inc.hip); the
+ * pairs left are aligned by the pair-form lane aligner as nwalign(query, ref, match, mismatch, gap_p, band = band,
+ * endsfree = TRUE) and reduced by C_eval_pair on the host, and the host replays the greedy choice.  With band >= 0 every
+ * screened pair is aligned.  Letters outside A/C/G/T: DADA2HIP_ERR_UNSUPPORTED.  A column total or a collapsed cell above
+ * INT32_MAX (NA in the reference) is DADA2HIP_ERR_INPUT.
+ * stats (optional, DADA2HIP_COLLAPSE_NSTATS int64 words): [0] columns after de-duplication, [1] candidate pairs after the
+ * join, [2] pairs scanned, [3] of them screened out, [4] rejected by the bound, [5] pairs aligned, [6] aligned pairs with
+ * mismatch + indel == 0, [7] batches, [8..11] host wall time in microseconds of join / scan / align / resolve, [12] of the
+ * whole call; the rest 0.
+ * dada2hip_collapse_pairs: what the scan kernel computes, for n (query, ref) pairs: out[4 i .. 4 i + 3] = screen (bit 0:
+ * substr(query, 1, min_overlap) occurs in ref, bit 1: substr(ref, 1, min_overlap) occurs in query), G (the best score of a
+ * gapless diagonal), m_max (the longest diagonal without a mismatch, 0 if none), decision (0 screened out, 1 rejected by
+ * G > match * m_max, 2 needs the alignment).
+ * dada2hip_nweval == nweval(s1, s2, match, mismatch, gap_p, homo_gap_p, band, endsfree, vec) (R/misc.R:222-225), vectorised:
+ * out[3 i .. 3 i + 2] = match, mismatch, indel of C_eval_pair on the alignment of pair i (vec != 0: C_nwvec, else C_nwalign);
+ * nwhamming is mismatch + indel. */
+#define DADA2HIP_COLLAPSE_NSTATS 16
+int dada2hip_collapse_nomismatch(int32_t nrow, int32_t ncol, const int32_t *mat, const char *const *seqs, int32_t min_overlap,
+                                 int32_t identical_only, int32_t band, int32_t match, int32_t mismatch, int32_t gap_p,
+                                 int32_t device, int32_t *into, int64_t *stats, char *errbuf, size_t errlen);
+int dada2hip_collapse_pairs(int32_t n, const char *const *queries, const char *const *refs, int32_t min_overlap, int32_t match,
+                            int32_t mismatch, int32_t device, int32_t *out, char *errbuf, size_t errlen);
+int dada2hip_nweval(int32_t n, const char *const *s1, const char *const *s2, int32_t match, int32_t mismatch, int32_t gap_p,
+                    int32_t homo_gap_p, int32_t band, int32_t endsfree, int32_t vec, int32_t device, int32_t *out,
+                    char *errbuf, size_t errlen);
 
 /* One b_compare round exposed for kernel-level parity tests and for bench.py's roofline leg:
  * compares every unique of `s` against unique `centre` exactly as CompareParallel does
