@@ -120,12 +120,19 @@ EXPORTS = [
     "dada2hip_mergers_forward", "dada2hip_mergers_reverse", "dada2hip_mergers_nmatch", "dada2hip_mergers_nmismatch",
     "dada2hip_mergers_nindel", "dada2hip_mergers_prefer", "dada2hip_mergers_accept", "dada2hip_mergers_free",
     "dada2hip_collapse_nomismatch", "dada2hip_collapse_pairs", "dada2hip_nweval",
+    "dada2hip_taxonomy_train", "dada2hip_taxonomy_free", "dada2hip_taxonomy_table", "dada2hip_taxonomy_assign",
 ]
 
 COLLAPSE_NSTATS = 16   # DADA2HIP_COLLAPSE_NSTATS
 # the int64 words of dada2hip_collapse_nomismatch's stats, in order (the *_us entries are host wall time in microseconds)
 COLLAPSE_STATS = ("columns_dedup", "candidate_pairs", "pairs_scanned", "pairs_screened_out", "pairs_bound_rejected", "pairs_aligned",
                   "aligned_ham0", "batches", "join_us", "scan_us", "align_us", "resolve_us", "total_us")
+
+TAXONOMY_NSTATS = 16   # DADA2HIP_TAXONOMY_NSTATS
+# the int64 words of dada2hip_taxonomy_train's and dada2hip_taxonomy_assign's stats, in order
+TAXONOMY_TRAIN_STATS = ("build_us", "upload_us", "table_bytes")
+TAXONOMY_STATS = ("classified", "slab_queries", "gather_queries", "took_reverse_complement", "launches", "prepare_us", "slab_device_us",
+                  "gather_device_us", "try_rc_device_us", "total_us")
 
 
 class CSampleInput(C.Structure):
@@ -266,6 +273,11 @@ def lib():
     L.dada2hip_collapse_nomismatch.argtypes = [ip, ip, vp, C.POINTER(cp), ip, ip, ip, ip, ip, ip, ip, vp, vp, cp, C.c_size_t]
     L.dada2hip_collapse_pairs.argtypes = [ip, C.POINTER(cp), C.POINTER(cp), ip, ip, ip, ip, vp, cp, C.c_size_t]
     L.dada2hip_nweval.argtypes = [ip, C.POINTER(cp), C.POINTER(cp), ip, ip, ip, ip, ip, ip, ip, ip, vp, cp, C.c_size_t]
+    L.dada2hip_taxonomy_train.argtypes = [ip, C.POINTER(cp), vp, ip, ip, vp, ip, C.POINTER(vp), vp, cp, C.c_size_t]
+    L.dada2hip_taxonomy_free.argtypes = [vp]
+    L.dada2hip_taxonomy_free.restype = None
+    L.dada2hip_taxonomy_table.argtypes = [vp, vp, cp, C.c_size_t]
+    L.dada2hip_taxonomy_assign.argtypes = [vp, ip, C.POINTER(cp), ip, vp, C.c_uint64, vp, vp, vp, vp, vp, cp, C.c_size_t]
     L.dada2hip_trim_cache.argtypes = []
     L.dada2hip_trim_cache.restype = None
     _lib = L

@@ -618,6 +618,222 @@ def collapse_no_mismatch(mat, seqs, min_overlap=20, order_by="abundance", identi
     return np.ascontiguousarray(out), names
 
 
+# ---- assignTaxonomy (R/taxonomy.R:65-160 on C_assign_taxonomy2, src/taxonomy.cpp) -----------------------------------------------
+TAX_LEVELS = ("Kingdom", "Phylum", "Class", "Order", "Family", "Genus", "Species")
+_TAX_UNSPECIFIED = "_DADA2_UNSPECIFIED"
+
+
+def read_fasta(path):
+    """(ids, sequences) of a plain or gzip FASTA file, as ShortRead::readFasta gives them: the whole header line behind '>' and
+    the record's lines joined, in upper case (a DNAStringSet holds upper case)."""
+    import gzip
+    with open(path, "rb") as fh:
+        magic = fh.read(2)
+    opener = gzip.open if magic == b"\x1f\x8b" else open
+    ids, seqs, cur = [], [], None
+    with opener(path, "rt") as fh:
+        for line in fh:
+            line = line.rstrip("\r\n")
+            if line.startswith(">"):
+                if cur is not None:
+                    seqs.append("".join(cur))
+                ids.append(line[1:])
+                cur = []
+            elif cur is not None:
+                cur.append(line.strip().upper())
+    if cur is not None:
+        seqs.append("".join(cur))
+    return ids, seqs
+
+
+def _r_strsplit(s, sep=";"):
+    """strsplit(s, sep)[[1]]: a trailing empty piece is dropped, and "" gives no piece."""
+    parts = s.split(sep)
+    if parts and parts[-1] == "":
+        parts.pop()
+    return parts
+
+
+def taxonomy_reference(refs, ids):
+    """The reference side of assignTaxonomy (R/taxonomy.R:76-122) from sequences and their id lines: references under 20 nt are
+    dropped, id whitespace trimmed, UNITE ids rewritten, the format checked, every taxonomy padded with ``_DADA2_UNSPECIFIED;`` to
+    the deepest one.  Returns (refs, genus_unq, ref_to_genus, genusmat): the kept references, the distinct taxonomy strings in
+    order of first occurrence, the 0-based genus of every kept reference and the int32 [ngenus, depth] level codes (per level the
+    distinct names numbered in order of first occurrence: the C code only tests them for equality)."""
+    import re
+    import warnings
+    if len(refs) != len(ids):
+        raise ValueError("One taxonomy per reference sequence is required.")
+    keep = [i for i, r in enumerate(refs) if len(r) >= 20]                      # MIN_REF_LEN
+    if len(keep) < len(refs):
+        warnings.warn("Some reference sequences were too short (<20nts) and were excluded.")
+    refs = [refs[i] for i in keep]
+    tax = [ids[i].strip() for i in keep]
+    if not tax:
+        raise ValueError("No reference sequences.")
+    if len(tax) >= 10 and all(re.search(r"FU\|re[pf]s", t) for t in tax[:10]):  # UNITE
+        def unite(t):
+            f = t.split("|")
+            t = f[4] if len(f) > 4 else ""
+            t = re.sub(r"[pcofg]__unidentified;", _TAX_UNSPECIFIED + ";", t)
+            t = re.sub(r";s__(\w+)_", ";s__", t, flags=re.ASCII)
+            return re.sub(r";s__sp$", ";" + _TAX_UNSPECIFIED, t)
+        tax = [unite(t) for t in tax]
+    if ";" not in tax[0]:
+        if len(tax[0].split()) == 3:
+            raise ValueError("Incorrect reference file format for assignTaxonomy (this looks like a file formatted for assignSpecies).")
+        raise ValueError("Incorrect reference file format for assignTaxonomy.")
+    depth = [len(_r_strsplit(t)) for t in tax]
+    td = max(depth)
+    tax = [t + (_TAX_UNSPECIFIED + ";") * (td - d) for t, d in zip(tax, depth)]
+    genus_unq = list(dict.fromkeys(tax))
+    pos = {g: k for k, g in enumerate(genus_unq)}
+    ref_to_genus = np.array([pos[t] for t in tax], dtype=np.int32)
+    rows = [_r_strsplit(g) for g in genus_unq]
+    if any(len(r) != td for r in rows):
+        raise ValueError("Incorrect reference file format for assignTaxonomy: a taxonomy does not end in ';'.")
+    genusmat = np.zeros((len(rows), td), dtype=np.int32)
+    for lvl in range(td):
+        code = {}
+        for g, r in enumerate(rows):
+            genusmat[g, lvl] = code.setdefault(r[lvl], len(code))
+    return refs, genus_unq, ref_to_genus, genusmat
+
+
+class TaxonomyModel:
+    """The trained classifier, resident on ``device``: ``TaxonomyModel(ref_fasta)`` or ``TaxonomyModel((refs, taxonomies))`` with
+    taxonomies the id lines ("Kingdom;Phylum;...;").  Train once, pass to assign_taxonomy as often as needed."""
+
+    def __init__(self, ref, device: int = 0):
+        if isinstance(ref, (str, bytes)) or hasattr(ref, "__fspath__"):
+            ids, seqs = read_fasta(ref)
+        else:
+            seqs, ids = ref
+            seqs, ids = [str(x).upper() for x in seqs], [str(x) for x in ids]
+        self._train(*taxonomy_reference(seqs, ids), device)
+
+    @classmethod
+    def from_parsed(cls, refs, genus_unq, ref_to_genus, genusmat, device: int = 0):
+        """A model from what taxonomy_reference returns (or an equivalent the caller built)."""
+        m = cls.__new__(cls)
+        m._train(list(refs), list(genus_unq), np.ascontiguousarray(ref_to_genus, dtype=np.int32), np.ascontiguousarray(genusmat, dtype=np.int32),
+                 device)
+        return m
+
+    def _train(self, refs, genus_unq, ref_to_genus, genusmat, device):
+        self.refs, self.genus_unq, self.ref_to_genus, self.genusmat = refs, genus_unq, ref_to_genus, genusmat
+        self.device = device
+        self.depth = int(self.genusmat.shape[1])
+        self._h = C.c_void_p()
+        st = np.zeros(_lib.TAXONOMY_NSTATS, dtype=np.int64)
+        gm = np.ascontiguousarray(self.genusmat)
+        eb = C.create_string_buffer(_EB)
+        _lib.check(_lib.lib().dada2hip_taxonomy_train(len(self.refs), _charpp(self.refs), self.ref_to_genus.ctypes.data, gm.shape[0], gm.shape[1],
+                                                      gm.ctypes.data, device, C.byref(self._h), st.ctypes.data, eb, _EB), eb)
+        self.stats = {k: int(st[i]) for i, k in enumerate(_lib.TAXONOMY_TRAIN_STATS)}
+
+    @property
+    def ngenus(self):
+        return len(self.genus_unq)
+
+    def table(self):
+        """The log-probability table read back from the device: float32 [ngenus, 65536] (diagnostic)."""
+        out = np.zeros((self.ngenus, 65536), dtype=np.float32)
+        eb = C.create_string_buffer(_EB)
+        _lib.check(_lib.lib().dada2hip_taxonomy_table(self._h, out.ctypes.data, eb, _EB), eb)
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().dada2hip_taxonomy_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def taxonomy_unifs(seed, n):
+    """The n uniforms the library draws from ``seed`` when it is given none (include/dada2hip.h: splitmix64 of the position)."""
+    with np.errstate(over="ignore"):
+        z = np.uint64(seed & 0xFFFFFFFFFFFFFFFF) + (np.arange(n, dtype=np.uint64) + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z ^= z >> np.uint64(31)
+    return (z >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+
+
+def assign_taxonomy_raw(seqs, model: TaxonomyModel, try_rc=False, seed=0, unifs=None, stats: dict = None):
+    """dada2hip_taxonomy_assign: {"tax" [n], "boot" [n, depth], "boot_tax" [n, 100], "ntie" [n, 101]}, 0-based genus indices
+    (-1: the query is shorter than 50 nt).  ``unifs``: nseq * 100 * ((max length - 7) // 8) doubles in [0, 1), laid out as the
+    reference's runif buffer; None: drawn from ``seed``."""
+    seqs = [seqs] if isinstance(seqs, str) else list(seqs)
+    n = len(seqs)
+    tax = np.zeros(n, dtype=np.int32)
+    boot = np.zeros((n, model.depth), dtype=np.int32)
+    boot_tax = np.zeros((n, 100), dtype=np.int32)
+    ntie = np.zeros((n, 101), dtype=np.int32)
+    st = np.zeros(_lib.TAXONOMY_NSTATS, dtype=np.int64)
+    u = None
+    if unifs is not None:
+        u = np.ascontiguousarray(unifs, dtype=np.float64).ravel()
+        need = n * 100 * (max(max((len(s) for s in seqs), default=0) - 7, 0) // 8)
+        if u.size < need:
+            raise ValueError("unifs holds %d values, the call needs %d." % (u.size, need))
+    eb = C.create_string_buffer(_EB)
+    _lib.check(_lib.lib().dada2hip_taxonomy_assign(model._h, n, _charpp(seqs), int(bool(try_rc)), None if u is None else u.ctypes.data,
+                                                   int(seed) & 0xFFFFFFFFFFFFFFFF, tax.ctypes.data, boot.ctypes.data, boot_tax.ctypes.data,
+                                                   ntie.ctypes.data, st.ctypes.data, eb, _EB), eb)
+    if stats is not None:
+        stats.update({k: int(st[i]) for i, k in enumerate(_lib.TAXONOMY_STATS)})
+    return {"tax": tax, "boot": boot, "boot_tax": boot_tax, "ntie": ntie}
+
+
+def taxonomy_table_out(genus_unq, tax, boot, min_boot=50):
+    """R/taxonomy.R:137-150: the [n, depth] object array of level names - per query the levels of its genus whose bootstrap
+    count reaches ``min_boot``, ``_DADA2_UNSPECIFIED`` and everything else None."""
+    td = boot.shape[1]
+    out = np.full((len(tax), td), None, dtype=object)
+    for i, g in enumerate(tax):
+        if g < 0:
+            continue
+        names = [x for x, b in zip(_r_strsplit(genus_unq[int(g)]), boot[i]) if b >= min_boot]
+        for l, x in enumerate(names):
+            out[i, l] = None if x == _TAX_UNSPECIFIED else x
+    return out
+
+
+def assign_taxonomy(seqs, ref, min_boot=50, try_rc=False, output_bootstraps=False, tax_levels=TAX_LEVELS, seed=0, unifs=None,
+                    device: int = 0):
+    """assignTaxonomy (R/taxonomy.R:65-160).  ``ref``: a reference FASTA (plain or gzip), (refs, taxonomies) or a TaxonomyModel.
+    Returns the [n, depth] object array of level names (None = NA), or with ``output_bootstraps`` {"tax", "boot", "levels"}.  The
+    bootstrap draws come from ``seed`` (or ``unifs``, see assign_taxonomy_raw) where the reference asks R's generator."""
+    import warnings
+    seqs = [seqs] if isinstance(seqs, str) else list(seqs)
+    if seqs and min(len(s) for s in seqs) < 50:
+        warnings.warn("Some sequences were shorter than 50 nts and will not receive a taxonomic classification.")
+    own = not isinstance(ref, TaxonomyModel)
+    model = TaxonomyModel(ref, device=device) if own else ref
+    try:
+        raw = assign_taxonomy_raw(seqs, model, try_rc=try_rc, seed=seed, unifs=unifs)
+        out = taxonomy_table_out(model.genus_unq, raw["tax"], raw["boot"], min_boot)
+        levels = list(tax_levels[: model.depth])
+    finally:
+        if own:
+            model.close()
+    if output_bootstraps:
+        return {"tax": out, "boot": raw["boot"], "levels": levels}
+    return out
+
+
 def calc_pA_device(reads, E, prior, device: int = 0):
     """calc_pA (src/pval.cpp:44-64) evaluated by the device kernel."""
     L = _lib.lib()

@@ -3559,6 +3559,9 @@ int dada2hip_nwalign(const char *s1, const char *s2, int32_t match, int32_t mism
 // ---- the sequence-table stage: collapseNoMismatch, nweval (R/multiSample.R:104-160, R/misc.R:216-225) ----
 #include "collapse_host.h"
 
+// ---- assignTaxonomy: the naive-Bayes 8-mer classifier (src/taxonomy.cpp) ----
+#include "taxonomy_host.h"
+
 // ---- result getters ------------------------------------------------------------------------------
 int32_t dada2hip_result_nclust(const dada2hip_result *r) { return r->nclust; }
 int32_t dada2hip_result_nraw(const dada2hip_result *r) { return r->nraw; }

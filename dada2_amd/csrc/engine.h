@@ -574,6 +574,26 @@ void launch_collapse_join(const SampleDev &S, int row0, int nrows, const unsigne
                           int ngroups, int KW, uint32_t *d_bits, hipStream_t st);
 void launch_collapse_scan(const SampleDev &S, const int2 *d_pairs, int npairs, int min_overlap, int match, int mismatch, int use_bound,
                           int4 *d_out, hipStream_t st);
+// assignTaxonomy (taxonomy.inc.hip).  T[65536][gpad]: the log-probability table, k-mer-major, genera padded to a multiple of 64.
+// A job is nq queries: k-mers karr[koff[q] .. koff[q + 1]) (sorted), replicate positions bpos[boff[q] + r * (len / 8) + i] into that
+// array (npass == 101; npass == 1 is the full pass alone), qid[q] the caller's index of the query (the tie hash).
+constexpr int TAX_THREADS = 256;
+struct TaxPart { float maxlogp; int32_t ntie; uint32_t hash; int32_t genus; };
+struct TaxJob {
+  const float *T;
+  int gpad, ngenus, ntiles, nq, npass;
+  const int32_t *koff;
+  const uint16_t *karr;
+  const long long *boff;
+  const uint16_t *bpos;
+  const int32_t *qid;
+  uint32_t seed_lo, seed_hi;
+  TaxPart *part;                 // [nq][npass][ntiles], k_tax_sums -> k_tax_combine
+  float *best;                   // [nq][npass]: the maximum, the genera at it, the winner
+  int32_t *ntie, *winner;
+};
+bool launch_tax_sums(const TaxJob &J, int slab_positions, hipStream_t st);
+void launch_tax_combine(const TaxJob &J, hipStream_t st);
 void launch_calc_pA(int n, const int32_t *d_reads, const double *d_E, const uint8_t *d_prior, double *d_out,
                     hipStream_t st);
 

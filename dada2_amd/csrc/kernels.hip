@@ -2894,6 +2894,8 @@ void launch_bimera_lr(const SampleDev &S, const int32_t *d_chunk_centre, const i
 
 #include "collapse.inc.hip"   // collapseNoMismatch: the prefix-key join and the diagonal scan
 
+#include "taxonomy.inc.hip"   // assignTaxonomy: the per-(query, tile) sums and their fold
+
 #include "rounds2.inc.hip"   // (the persistent round tail, rounds3.inc.hip, is the translation unit tail.hip)
 
 }  // namespace d2

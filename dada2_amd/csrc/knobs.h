@@ -67,7 +67,8 @@ struct Knobs {
   int collapse_batch = 0;             // DADA2HIP_COLLAPSE_BATCH=n      collapseNoMismatch: queries per batch (0 = automatic: 4 096)
   int collapse_scan = 1;              // DADA2HIP_COLLAPSE_SCAN=0       ... every screened pair is aligned (the diagonal bound is not used)
   int collapse_join = 1;              // DADA2HIP_COLLAPSE_JOIN=0       ... every (query, ref) pair is scanned (no prefix-key join)
-  bool derep_zlib = false;            // DADA2HIP_DEREP_INFLATE=zlib    .gz files through zlib's streaming inflate even where libdeflate is installed
+  int tax_slab = 256;                 // DADA2HIP_TAX_SLAB=n            assignTaxonomy: queries of at most n k-mers are summed out of an LDS slab (0 = every query gathers from the table; at most 512)
+  bool derep_zlib = false;           // DADA2HIP_DEREP_INFLATE=zlib    .gz files through zlib's streaming inflate even where libdeflate is installed
   bool derep_times = false;           // DADA2HIP_DEREP_TIMES=1         stderr: phases of a dada2hip_derep_fastq call
   // (read once per process, when the host pool / the allocation cache are created: DADA2HIP_HOST_THREADS, DADA2HIP_ALLOC_CACHE,
   //  DADA2HIP_ALLOC_CACHE_GB)
@@ -122,6 +123,7 @@ struct Knobs {
     if (const char *e = S("DADA2HIP_BIMERA_TIMES")) k.bimera_times = !std::strcmp(e, "1");
     k.collapse_batch = I("DADA2HIP_COLLAPSE_BATCH", 0); k.collapse_scan = I("DADA2HIP_COLLAPSE_SCAN", 1);
     k.collapse_join = I("DADA2HIP_COLLAPSE_JOIN", 1);
+    k.tax_slab = I("DADA2HIP_TAX_SLAB", 256);
     if (const char *e = S("DADA2HIP_DEREP_INFLATE")) k.derep_zlib = !std::strcmp(e, "zlib");
     if (const char *e = S("DADA2HIP_DEREP_TIMES")) k.derep_times = !std::strcmp(e, "1");
     k.host_threads = I("DADA2HIP_HOST_THREADS", 0);

@@ -19,6 +19,8 @@
  *                                                   (src/evaluate.cpp:18-62, :73-114, :124-174)
  *   dada2hip_collapse_nomismatch <- collapseNoMismatch()  R/multiSample.R:104-160 (grepl screen + nwhamming per pair)
  *   dada2hip_nweval         <- nweval() / nwhamming()  R/misc.R:216-225
+ *   dada2hip_taxonomy_*     <- C_assign_taxonomy2() src/taxonomy.cpp:206-338  (`_dada2_C_assign_taxonomy2`; R/taxonomy.R:135), split into
+ *                              the model (:219-270, built once, resident in HBM) and the classification of queries (:113-200)
  *   dada2hip_derep_*        <- derepFastq() / qtables2()  R/sequenceIO.R:45-124, :150-183 (host-side C++, zlib)
  *
  * Conventions: plain C, no exceptions cross the boundary.  Every call returns 0 on success or a
@@ -45,6 +47,8 @@
  *   DADA2HIP_COLLAPSE_BATCH=<n>        dada2hip_collapse_nomismatch: queries per batch (default 0 = automatic)
  *   DADA2HIP_COLLAPSE_SCAN=0           ... every screened pair is aligned (the bound of the diagonal scan is not used)
  *   DADA2HIP_COLLAPSE_JOIN=0           ... every (query, ref) pair is scanned (no prefix-key join)
+ *   DADA2HIP_TAX_SLAB=<n>              dada2hip_taxonomy_assign: queries of at most n valid k-mers are summed out of an LDS slab, longer
+ *                                      ones gather from the table (default 256, at most 512; 0 = every query gathers)
  *   DADA2HIP_PROFILE=1, DADA2HIP_V2_SUMMARY, DADA2HIP_V2_DEBUG   per-launch device times in the stats; traces on stderr
  * Test / tuning knobs (sizes of rings and grids, forced growth paths, injected failures) are listed with their meaning in
  * knobs.h and DESIGN.md §10b; they are not part of the interface.
@@ -390,6 +394,50 @@ int dada2hip_collapse_pairs(int32_t n, const char *const *queries, const char *c
 int dada2hip_nweval(int32_t n, const char *const *s1, const char *const *s2, int32_t match, int32_t mismatch, int32_t gap_p,
                     int32_t homo_gap_p, int32_t band, int32_t endsfree, int32_t vec, int32_t device, int32_t *out,
                     char *errbuf, size_t errlen);
+
+/* ---- assignTaxonomy: the naive-Bayes 8-mer classifier -----------------------------------------------
+ * dada2hip_taxonomy_train builds the model of C_assign_taxonomy2 (src/taxonomy.cpp:219-270) from nref reference sequences,
+ * ref_to_genus[nref] (0-BASED) and genusmat (ngenus x nlevel integer level codes, ROW-major; only their equality is used) and
+ * keeps it on `device`: per genus g and 8-mer w, logf((cnt[g][w] + prior[w]) / (M_g + 1)) with cnt the references of g that
+ * contain w, prior[w] = (float)((references that contain w + 0.5) / (1.0 + nref)) and M_g the references of g.  The table is
+ * computed on the host (counts from each reference's distinct k-mers, the logarithm by the host's logf) and is bit-equal to the
+ * reference's; on the device it lies k-mer-major with the genera padded to a multiple of 64.  DADA2HIP_ERR_INPUT: a reference
+ * shorter than 8, ref_to_genus out of range, ngenus == 0, nref >= 2^24.  stats (optional, DADA2HIP_TAXONOMY_NSTATS int64 words):
+ * [0] host microseconds of the build, [1] of the upload, [2] bytes of the table.
+ * dada2hip_taxonomy_table (diagnostic) reads the table back: out[g * 65536 + w], ngenus x 65536 floats.
+ *
+ * dada2hip_taxonomy_assign classifies nseq queries as AssignParallel does (src/taxonomy.cpp:143-199).  Outputs are 0-BASED and
+ * ROW-major: tax[nseq] the best genus, boot_tax[j * 100 + r] the best genus of bootstrap replicate r, boot[j * nlevel + l] the
+ * replicates whose genus agrees with tax[j] on levels 0..l, ntie[j * 101 + p] the number of genera whose sum equals the maximum
+ * of pass p (0: the full pass, 1 + r: replicate r).  A query shorter than 50 gets tax = -1, boot = 0, boot_tax = -1, ntie = 0 (NA
+ * in the reference); one longer than 9999 is DADA2HIP_ERR_INPUT.  K-mers with a letter outside A/C/G/T are skipped.
+ * Each sum is taken sequentially in float in the reference's order (the sorted k-mers; the draws of a replicate), over the
+ * reference's table: the sums are the reference's bits, so the maximum and the set of genera at it are the reference's.  Inside
+ * that set the reference draws from std::random_device; here the winner is the genus with the smallest 32-bit hash of (seed,
+ * query, pass, genus), equal hashes going to the smaller genus - uniform over the set, deterministic for a seed.  The hash is
+ * f(f(f(f(f(lo ^ 0x9E3779B9) ^ hi) ^ query) ^ pass) ^ genus) with lo / hi the halves of seed and f MurmurHash3's 32-bit finaliser.
+ * Replicate r of query j draws k-mer (int)(arraylen * u) of its sorted array, arraylen / 8 times, with u taken in the
+ * reference's layout (:181-186): query j starts at unifs[j * max_arraylen] and consumes 100 * (arraylen / 8) values in a row,
+ * max_arraylen = max(length) - 7 over ALL queries; neighbouring queries overlap, as in the reference.  unifs holds
+ * nseq * 100 * (max_arraylen / 8) doubles in [0, 1) (what Rcpp::runif returns there); with unifs == NULL value i of that buffer
+ * is z = seed + (i + 1) * 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ * z ^= z >> 31; u = (z >> 11) * 2^-53 (splitmix64), in 64-bit unsigned arithmetic.
+ * try_rc != 0 (:169-177): the full pass also runs on the reverse complement's k-mers; where its maximum is strictly greater as a
+ * float, its k-mers serve the query's 101 passes.
+ * stats (optional, DADA2HIP_TAXONOMY_NSTATS int64 words): [0] queries classified, [1] of them by the slab instance, [2] by the
+ * gather instance, [3] queries that took their reverse complement, [4] kernel launches, [5] host microseconds of the
+ * preparation, [6] device microseconds in the slab instance, [7] in the gather instance, [8] in the try_rc passes, [9] host
+ * microseconds of the whole call. */
+#define DADA2HIP_TAXONOMY_NSTATS 16
+typedef struct dada2hip_taxonomy dada2hip_taxonomy;
+int dada2hip_taxonomy_train(int32_t nref, const char *const *refs, const int32_t *ref_to_genus, int32_t ngenus, int32_t nlevel,
+                            const int32_t *genusmat, int32_t device, dada2hip_taxonomy **out, int64_t *stats, char *errbuf,
+                            size_t errlen);
+void dada2hip_taxonomy_free(dada2hip_taxonomy *m);
+int dada2hip_taxonomy_table(const dada2hip_taxonomy *m, float *out, char *errbuf, size_t errlen);
+int dada2hip_taxonomy_assign(const dada2hip_taxonomy *m, int32_t nseq, const char *const *seqs, int32_t try_rc, const double *unifs,
+                             uint64_t seed, int32_t *tax, int32_t *boot, int32_t *boot_tax, int32_t *ntie, int64_t *stats,
+                             char *errbuf, size_t errlen);
 
 /* One b_compare round exposed for kernel-level parity tests and for bench.py's roofline leg:
  * compares every unique of `s` against unique `centre` exactly as CompareParallel does
