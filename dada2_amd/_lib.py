@@ -121,6 +121,8 @@ EXPORTS = [
     "dada2hip_mergers_nindel", "dada2hip_mergers_prefer", "dada2hip_mergers_accept", "dada2hip_mergers_free",
     "dada2hip_collapse_nomismatch", "dada2hip_collapse_pairs", "dada2hip_nweval",
     "dada2hip_taxonomy_train", "dada2hip_taxonomy_free", "dada2hip_taxonomy_table", "dada2hip_taxonomy_assign",
+    "dada2hip_species_open", "dada2hip_species_free", "dada2hip_species_match", "dada2hip_species_hits_offsets",
+    "dada2hip_species_hits_refs", "dada2hip_species_hits_free",
 ]
 
 COLLAPSE_NSTATS = 16   # DADA2HIP_COLLAPSE_NSTATS
@@ -133,6 +135,11 @@ TAXONOMY_NSTATS = 16   # DADA2HIP_TAXONOMY_NSTATS
 TAXONOMY_TRAIN_STATS = ("build_us", "upload_us", "table_bytes")
 TAXONOMY_STATS = ("classified", "slab_queries", "gather_queries", "took_reverse_complement", "launches", "prepare_us", "slab_device_us",
                   "gather_device_us", "try_rc_device_us", "total_us")
+
+SPECIES_NSTATS = 16   # DADA2HIP_SPECIES_NSTATS
+# the int64 words of dada2hip_species_open's and dada2hip_species_match's stats, in order
+SPECIES_STATS = ("references", "bases", "windows", "windows_past_bitmap", "candidates", "candidate_reruns", "hits", "launches",
+                 "seed_host_us", "seed_device_us", "verify_host_us", "verify_device_us", "total_us", "resident_bytes")
 
 
 class CSampleInput(C.Structure):
@@ -278,6 +285,16 @@ def lib():
     L.dada2hip_taxonomy_free.restype = None
     L.dada2hip_taxonomy_table.argtypes = [vp, vp, cp, C.c_size_t]
     L.dada2hip_taxonomy_assign.argtypes = [vp, ip, C.POINTER(cp), ip, vp, C.c_uint64, vp, vp, vp, vp, vp, cp, C.c_size_t]
+    L.dada2hip_species_open.argtypes = [ip, C.POINTER(cp), ip, C.POINTER(vp), vp, cp, C.c_size_t]
+    L.dada2hip_species_free.argtypes = [vp]
+    L.dada2hip_species_free.restype = None
+    L.dada2hip_species_match.argtypes = [vp, ip, C.POINTER(cp), ip, C.POINTER(vp), vp, cp, C.c_size_t]
+    L.dada2hip_species_hits_offsets.argtypes = [vp]
+    L.dada2hip_species_hits_offsets.restype = C.POINTER(C.c_int64)
+    L.dada2hip_species_hits_refs.argtypes = [vp]
+    L.dada2hip_species_hits_refs.restype = C.POINTER(C.c_int32)
+    L.dada2hip_species_hits_free.argtypes = [vp]
+    L.dada2hip_species_hits_free.restype = None
     L.dada2hip_trim_cache.argtypes = []
     L.dada2hip_trim_cache.restype = None
     _lib = L

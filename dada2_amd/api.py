@@ -834,6 +834,177 @@ def assign_taxonomy(seqs, ref, min_boot=50, try_rc=False, output_bootstraps=Fals
     return out
 
 
+# ---- assignSpecies / addSpecies (R/taxonomy.R:162-360; the matching itself is dada2hip_species_match) --------------------------
+def _r_strsplit_ws(s):
+    """strsplit(s, "\\s")[[1]]: one separator per whitespace character (two blanks leave an empty piece between them), a trailing
+    empty piece dropped, "" gives no piece."""
+    import re
+    parts = re.split(r"\s", s, flags=re.ASCII)
+    if parts and parts[-1] == "":
+        parts.pop()
+    return parts
+
+
+def species_reference(ids):
+    """R/taxonomy.R:255-263 on the id lines of a species reference (">SeqID genus species"): the format check on the FIRST id, then
+    (genus, species) = tokens 2 and 3 of every id, None where an id has fewer tokens."""
+    ids = [str(x) for x in ids]
+    if not ids:
+        raise ValueError("No reference sequences.")
+    if not len(_r_strsplit_ws(ids[0])) >= 3:
+        if ids[0].count(";") >= 3:
+            raise ValueError("Incorrect reference file format for assignSpecies (this looks like a file formatted for assignTaxonomy).")
+        raise ValueError("Incorrect reference file format for assignSpecies.")
+    toks = [_r_strsplit_ws(i) for i in ids]
+    return [t[1] if len(t) > 1 else None for t in toks], [t[2] if len(t) > 2 else None for t in toks]
+
+
+class SpeciesModel:
+    """The references of assignSpecies, resident on ``device``: ``SpeciesModel(ref_fasta)`` or ``SpeciesModel((refs, ids))``.  Open
+    once, pass to species_hits / assign_species / add_species as often as needed.  A FASTA file is read as ShortRead reads it
+    (upper case); sequences handed over directly are taken as they are, and only upper-case A/C/G/T can be matched."""
+
+    def __init__(self, ref, device: int = 0):
+        if isinstance(ref, (str, bytes)) or hasattr(ref, "__fspath__"):
+            ids, seqs = read_fasta(ref)
+        else:
+            seqs, ids = ref
+            seqs, ids = [str(x) for x in seqs], [str(x) for x in ids]
+        if len(seqs) != len(ids):
+            raise ValueError("One id per reference sequence is required.")
+        self.genus, self.species = species_reference(ids)
+        self.refs, self.ids, self.device = seqs, ids, device
+        self._h = C.c_void_p()
+        st = np.zeros(_lib.SPECIES_NSTATS, dtype=np.int64)
+        eb = C.create_string_buffer(_EB)
+        _lib.check(_lib.lib().dada2hip_species_open(len(seqs), _charpp(seqs), device, C.byref(self._h), st.ctypes.data, eb, _EB), eb)
+        self.stats = {k: int(st[i]) for i, k in enumerate(_lib.SPECIES_STATS)}
+
+    @property
+    def nref(self):
+        return len(self.refs)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().dada2hip_species_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _check_species_queries(seqs):
+    """taxonomy.R:254 (C_isACGT), and an empty query, which a PDict does not take."""
+    for s in seqs:
+        if not s:
+            raise ValueError("An empty query sequence.")
+        if s.strip("ACGT"):
+            raise ValueError("Non-ACGT characters present in the query sequences.")
+
+
+def species_hits(seqs, model: SpeciesModel, try_rc=False, stats: dict = None):
+    """dada2hip_species_match: per query the int32 array of the 0-based references it occurs in (with ``try_rc``: it or its
+    reverse complement), ascending, each reference once."""
+    seqs = [seqs] if isinstance(seqs, str) else [str(s) for s in seqs]
+    _check_species_queries(seqs)
+    L = _lib.lib()
+    h = C.c_void_p()
+    st = np.zeros(_lib.SPECIES_NSTATS, dtype=np.int64)
+    eb = C.create_string_buffer(_EB)
+    _lib.check(L.dada2hip_species_match(model._h, len(seqs), _charpp(seqs), int(bool(try_rc)), C.byref(h), st.ctypes.data, eb, _EB), eb)
+    try:
+        off = np.ctypeslib.as_array(L.dada2hip_species_hits_offsets(h), shape=(len(seqs) + 1,)).copy()
+        refs = np.ctypeslib.as_array(L.dada2hip_species_hits_refs(h), shape=(int(off[-1]),)).copy() if off[-1] else np.zeros(0, dtype=np.int32)
+    finally:
+        L.dada2hip_species_hits_free(h)
+    if stats is not None:
+        stats.update({k: int(st[i]) for i, k in enumerate(_lib.SPECIES_STATS)})
+    return [refs[off[j]: off[j + 1]] for j in range(len(seqs))]
+
+
+def _map_hits(idx, names, keep):
+    """mapHits (R/taxonomy.R:163-171) on the reference indices of one query."""
+    hits = [names[int(i)] for i in idx]
+    hits = ["Escherichia/Shigella" if h is not None and ("Escherichia" in h or "Shigella" in h) else h for h in hits]
+    unq = set(hits)
+    if len(unq) > keep:
+        return None
+    named = sorted(h for h in unq if h is not None)              # (sort() drops NA; by code point here)
+    return "/".join(named) if named else None
+
+
+def species_table_out(hits, genus, species, keep):
+    """R/taxonomy.R:282-283: the [n, 2] object array (Genus, Species; None = NA) from per-query reference indices.  ``keep``: the
+    most distinct species names a query may have (math.inf for all); the genus column always allows one."""
+    out = np.full((len(hits), 2), None, dtype=object)
+    for i, idx in enumerate(hits):
+        out[i, 0] = _map_hits(idx, genus, 1)
+        out[i, 1] = _map_hits(idx, species, keep)
+    return out
+
+
+def assign_species(seqs, ref, allow_multiple=False, try_rc=False, n=2000, verbose=False, device: int = 0):
+    """assignSpecies (R/taxonomy.R:240-289).  ``ref``: a species FASTA (plain or gzip), (refs, ids) or a SpeciesModel.  Returns the
+    [n, 2] object array (Genus, Species; None = NA).  ``allow_multiple``: False, True or the largest number of species to join.
+    ``n`` (the reference's chunk of queries per PDict) is accepted and changes nothing here."""
+    import math
+    keep = (math.inf if allow_multiple else 1) if isinstance(allow_multiple, (bool, np.bool_)) else int(allow_multiple)
+    seqs = [seqs] if isinstance(seqs, str) else [str(s) for s in seqs]
+    own = not isinstance(ref, SpeciesModel)
+    if own and (isinstance(ref, (str, bytes)) or hasattr(ref, "__fspath__")):
+        ids, refs = read_fasta(ref)                              # (the reference reads the file, then checks the queries, then the ids)
+        ref = (refs, ids)
+    _check_species_queries(seqs)
+    model = SpeciesModel(ref, device=device) if own else ref
+    try:
+        out = species_table_out(species_hits(seqs, model, try_rc=try_rc), model.genus, model.species, keep)
+    finally:
+        if own:
+            model.close()
+    if verbose:
+        print(sum(1 for x in out[:, 1] if x is not None), "out of", len(seqs), "were assigned to the species level.")
+    return out
+
+
+def match_genera(gen_tax, gen_binom, split_glyph="/"):
+    """matchGenera (R/taxonomy.R:175-185): does the curated genus name agree with the binomial's genus - equal, or the binomial's
+    genus followed by a blank, "_" or the glyph at the start of the curated name (Clostridium groups), or behind the glyph at its
+    end (split genera).  ``gen_binom`` goes into the regular expressions unescaped, as in the reference."""
+    import re
+    if gen_tax is None or gen_binom is None or len(gen_tax) == 0 or len(gen_binom) == 0:
+        return False
+    return bool(gen_tax == gen_binom or re.search("^" + gen_binom + "[ _" + split_glyph + "]", gen_tax)
+                or re.search(split_glyph + gen_binom + "$", gen_tax))
+
+
+def add_species(taxtab, seqs, ref, colnames=None, allow_multiple=False, try_rc=False, n=2000, verbose=False, device: int = 0):
+    """addSpecies (R/taxonomy.R:347-360): ``taxtab`` [n, ncol] (the output of assign_taxonomy for ``seqs``, the reference's row
+    names) with a Species column appended - the species of assign_species where its genus agrees (match_genera) with the table's
+    genus column, the one ``colnames`` calls "Genus", else the last; None elsewhere."""
+    taxtab = np.asarray(taxtab, dtype=object)
+    if taxtab.ndim != 2 or taxtab.shape[0] != len(seqs):
+        raise ValueError("One row of the taxonomic table per sequence is required.")
+    binom = assign_species(seqs, ref, allow_multiple=allow_multiple, try_rc=try_rc, n=n, verbose=verbose, device=device)
+    gcol = list(colnames).index("Genus") if colnames is not None and "Genus" in list(colnames) else taxtab.shape[1] - 1
+    out = np.full((taxtab.shape[0], taxtab.shape[1] + 1), None, dtype=object)
+    out[:, :-1] = taxtab
+    for i in range(taxtab.shape[0]):
+        if match_genera(taxtab[i, gcol], binom[i, 0]):
+            out[i, -1] = binom[i, 1]
+    if verbose:
+        print("Of which", sum(1 for x in out[:, -1] if x is not None), "had genera consistent with the input table.")
+    return out
+
+
 def calc_pA_device(reads, E, prior, device: int = 0):
     """calc_pA (src/pval.cpp:44-64) evaluated by the device kernel."""
     L = _lib.lib()

@@ -3562,6 +3562,9 @@ int dada2hip_nwalign(const char *s1, const char *s2, int32_t match, int32_t mism
 // ---- assignTaxonomy: the naive-Bayes 8-mer classifier (src/taxonomy.cpp) ----
 #include "taxonomy_host.h"
 
+// ---- assignSpecies: exact substring matching against resident references (R/taxonomy.R:264-280) ----
+#include "species_host.h"
+
 // ---- result getters ------------------------------------------------------------------------------
 int32_t dada2hip_result_nclust(const dada2hip_result *r) { return r->nclust; }
 int32_t dada2hip_result_nraw(const dada2hip_result *r) { return r->nraw; }

@@ -594,6 +594,32 @@ struct TaxJob {
 };
 bool launch_tax_sums(const TaxJob &J, int slab_positions, hipStream_t st);
 void launch_tax_combine(const TaxJob &J, hipStream_t st);
+// assignSpecies (species.inc.hip).  The references lie resident as 2-bit words (base k of a word at bits 2k..2k+1, A C G T = 0 1 2 3)
+// with a parallel plane of one bit per base, set where the letter is not an upper-case A/C/G/T (its 2-bit code is then 0); row r
+// starts at word woff[r] (a multiple of 2, so at bit 16 woff[r] of the plane) and has len[r] bases.  Both arrays are padded behind
+// the last row.  A call's patterns (queries and, with try_rc, their reverse complements) are packed alike: pattern t is
+// pat_len[t] bases from word pat_woff[t] of pat_words and reports under query pat_query[t].  keys: the distinct prefix keys,
+// ascending inside each key length's group; groups[g] = {key length, first key, number of keys}; the patterns of key k are
+// key_pats[key_pat_off[k] .. key_pat_off[k + 1]).
+constexpr int SP_BITMAP_LOG2 = 18, SP_BITMAP_WORDS = 1 << (SP_BITMAP_LOG2 - 5);   // 32 KB of LDS per block
+struct SpCand { int32_t ref, pos, key; };
+struct SpeciesRefs {
+  const uint32_t *words, *nplane;
+  const long long *woff;
+  const int32_t *len;
+};
+struct SpeciesKeys {
+  const unsigned long long *keys;
+  const int32_t *groups;
+  int ngroups, nkeys;
+  const int32_t *key_pat_off, *key_pats, *pat_woff, *pat_len, *pat_query;
+  const uint32_t *pat_words;
+};
+void launch_species_bitmap(const SpeciesKeys &K, uint32_t *d_bitmap, hipStream_t st);
+void launch_species_seed(const SpeciesRefs &R, int r0, int r1, const SpeciesKeys &K, const uint32_t *d_bitmap, SpCand *d_cand,
+                         unsigned long long cap, unsigned long long *d_counters, hipStream_t st);
+void launch_species_verify(const SpeciesRefs &R, const SpeciesKeys &K, const SpCand *d_cand, unsigned long long ncand,
+                           unsigned long long *d_hits, unsigned long long hit_cap, unsigned long long *d_counters, hipStream_t st);
 void launch_calc_pA(int n, const int32_t *d_reads, const double *d_E, const uint8_t *d_prior, double *d_out,
                     hipStream_t st);
 

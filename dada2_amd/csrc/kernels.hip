@@ -2896,6 +2896,8 @@ void launch_bimera_lr(const SampleDev &S, const int32_t *d_chunk_centre, const i
 
 #include "taxonomy.inc.hip"   // assignTaxonomy: the per-(query, tile) sums and their fold
 
+#include "species.inc.hip"   // assignSpecies: the prefix-key seed over the resident references and the verification
+
 #include "rounds2.inc.hip"   // (the persistent round tail, rounds3.inc.hip, is the translation unit tail.hip)
 
 }  // namespace d2

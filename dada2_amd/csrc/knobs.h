@@ -68,6 +68,8 @@ struct Knobs {
   int collapse_scan = 1;              // DADA2HIP_COLLAPSE_SCAN=0       ... every screened pair is aligned (the diagonal bound is not used)
   int collapse_join = 1;              // DADA2HIP_COLLAPSE_JOIN=0       ... every (query, ref) pair is scanned (no prefix-key join)
   int tax_slab = 256;                 // DADA2HIP_TAX_SLAB=n            assignTaxonomy: queries of at most n k-mers are summed out of an LDS slab (0 = every query gathers from the table; at most 512)
+  int species_cand = 1 << 20;         // DADA2HIP_SPECIES_CAND=n        assignSpecies: records of the candidate buffer and of the hit buffer (a launch that counts more is re-run in pieces)
+  int species_chunk = 8192;           // DADA2HIP_SPECIES_CHUNK=n       ... distinct queries per pass over the references (at most 8 192: the presence bitmap is sized for it)
   bool derep_zlib = false;           // DADA2HIP_DEREP_INFLATE=zlib    .gz files through zlib's streaming inflate even where libdeflate is installed
   bool derep_times = false;           // DADA2HIP_DEREP_TIMES=1         stderr: phases of a dada2hip_derep_fastq call
   // (read once per process, when the host pool / the allocation cache are created: DADA2HIP_HOST_THREADS, DADA2HIP_ALLOC_CACHE,
@@ -124,6 +126,7 @@ struct Knobs {
     k.collapse_batch = I("DADA2HIP_COLLAPSE_BATCH", 0); k.collapse_scan = I("DADA2HIP_COLLAPSE_SCAN", 1);
     k.collapse_join = I("DADA2HIP_COLLAPSE_JOIN", 1);
     k.tax_slab = I("DADA2HIP_TAX_SLAB", 256);
+    k.species_cand = I("DADA2HIP_SPECIES_CAND", 1 << 20); k.species_chunk = I("DADA2HIP_SPECIES_CHUNK", 8192);
     if (const char *e = S("DADA2HIP_DEREP_INFLATE")) k.derep_zlib = !std::strcmp(e, "zlib");
     if (const char *e = S("DADA2HIP_DEREP_TIMES")) k.derep_times = !std::strcmp(e, "1");
     k.host_threads = I("DADA2HIP_HOST_THREADS", 0);

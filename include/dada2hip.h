@@ -49,6 +49,9 @@
  *   DADA2HIP_COLLAPSE_JOIN=0           ... every (query, ref) pair is scanned (no prefix-key join)
  *   DADA2HIP_TAX_SLAB=<n>              dada2hip_taxonomy_assign: queries of at most n valid k-mers are summed out of an LDS slab, longer
  *                                      ones gather from the table (default 256, at most 512; 0 = every query gathers)
+ *   DADA2HIP_SPECIES_CAND=<n>          dada2hip_species_match: records of the candidate and hit buffers (default 1 048 576; a launch
+ *                                      that counts more is run again in pieces)
+ *   DADA2HIP_SPECIES_CHUNK=<n>         ... distinct queries per pass over the references (default and at most 8 192)
  *   DADA2HIP_PROFILE=1, DADA2HIP_V2_SUMMARY, DADA2HIP_V2_DEBUG   per-launch device times in the stats; traces on stderr
  * Test / tuning knobs (sizes of rings and grids, forced growth paths, injected failures) are listed with their meaning in
  * knobs.h and DESIGN.md §10b; they are not part of the interface.
@@ -438,6 +441,39 @@ int dada2hip_taxonomy_table(const dada2hip_taxonomy *m, float *out, char *errbuf
 int dada2hip_taxonomy_assign(const dada2hip_taxonomy *m, int32_t nseq, const char *const *seqs, int32_t try_rc, const double *unifs,
                              uint64_t seed, int32_t *tax, int32_t *boot, int32_t *boot_tax, int32_t *ntie, int64_t *stats,
                              char *errbuf, size_t errlen);
+
+/* ---- assignSpecies: exact matching against a species reference (R/taxonomy.R:240-289) ------------------------------------------
+ * What is matched is R/taxonomy.R:264-280: per chunk of equal-length queries a PDict, vcountPDict(...) > 0 over every reference,
+ * and with tryRC the same over the references' reverse complements - query q hits reference r exactly when q (with try_rc: q or
+ * its reverse complement) occurs in r as a substring.  The match is fixed = TRUE: a reference position holding any letter other
+ * than upper-case A/C/G/T (N, IUPAC codes, lower case) matches nothing, so an occurrence must lie on A/C/G/T only.  Nothing here
+ * is approximate and there are no ties: the hit lists are the reference's bit for bit.  The id parsing, mapHits, matchGenera and
+ * addSpecies (:251-263, :163-185, :281-360) are dada2_amd/api.py's.
+ *
+ * dada2hip_species_open packs nref reference sequences (2-bit words, a 1-bit plane of the other letters, row offsets and
+ * lengths) and keeps them on `device`; a reference may be empty.  DADA2HIP_ERR_INPUT: nref == 0.  stats as below ([0], [1], [12],
+ * [13] are set).
+ * dada2hip_species_match reports, per query, the 0-based indices of the references it hits, ascending, each once however many
+ * positions or strands match: offsets[nseq + 1] into refs.  Equal queries are matched once.  A query longer than every reference
+ * has no hits.  DADA2HIP_ERR_INPUT, checked before any device work: a query with a letter other than upper-case A/C/G/T
+ * ("Non-ACGT characters present in the query sequences.", :254), an empty query.  Calls on one handle take turns.
+ * stats (optional, DADA2HIP_SPECIES_NSTATS int64 words): [0] references, [1] their bases, [2] windows looked up in the presence
+ * bitmap (windows inside one reference that touch no other letter, per key length and query chunk), [3] of them past the bitmap,
+ * [4] candidates (windows equal to a prefix key), [5] launches of the seed kernel thrown away because they counted more
+ * candidates than DADA2HIP_SPECIES_CAND holds and run again in pieces, [6] entries of refs, [7] kernel launches, [8] host and
+ * [9] device microseconds of the seed kernel, [10] host and [11] device microseconds of the verification, [12] host
+ * microseconds of the whole call, [13] (open) bytes resident on the device. */
+#define DADA2HIP_SPECIES_NSTATS 16
+typedef struct dada2hip_species dada2hip_species;
+int dada2hip_species_open(int32_t nref, const char *const *refs, int32_t device, dada2hip_species **out, int64_t *stats, char *errbuf,
+                          size_t errlen);
+void dada2hip_species_free(dada2hip_species *m);
+typedef struct dada2hip_species_hits dada2hip_species_hits;
+int dada2hip_species_match(const dada2hip_species *m, int32_t nseq, const char *const *seqs, int32_t try_rc,
+                           dada2hip_species_hits **out, int64_t *stats, char *errbuf, size_t errlen);
+const int64_t *dada2hip_species_hits_offsets(const dada2hip_species_hits *h);   /* nseq + 1 */
+const int32_t *dada2hip_species_hits_refs(const dada2hip_species_hits *h);      /* 0-based, ascending per query */
+void dada2hip_species_hits_free(dada2hip_species_hits *h);
 
 /* One b_compare round exposed for kernel-level parity tests and for bench.py's roofline leg:
  * compares every unique of `s` against unique `centre` exactly as CompareParallel does
