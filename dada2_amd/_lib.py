@@ -123,6 +123,7 @@ EXPORTS = [
     "dada2hip_taxonomy_train", "dada2hip_taxonomy_free", "dada2hip_taxonomy_table", "dada2hip_taxonomy_assign",
     "dada2hip_species_open", "dada2hip_species_free", "dada2hip_species_match", "dada2hip_species_hits_offsets",
     "dada2hip_species_hits_refs", "dada2hip_species_hits_free",
+    "dada2hip_filter_open", "dada2hip_filter_free", "dada2hip_filter_reads", "dada2hip_filter_fastq", "dada2hip_filter_fastq_paired",
 ]
 
 COLLAPSE_NSTATS = 16   # DADA2HIP_COLLAPSE_NSTATS
@@ -140,6 +141,23 @@ SPECIES_NSTATS = 16   # DADA2HIP_SPECIES_NSTATS
 # the int64 words of dada2hip_species_open's and dada2hip_species_match's stats, in order
 SPECIES_STATS = ("references", "bases", "windows", "windows_past_bitmap", "candidates", "candidate_reruns", "hits", "launches",
                  "seed_host_us", "seed_device_us", "verify_host_us", "verify_device_us", "total_us", "resident_bytes")
+
+FILTER_NSTATS = 32   # DADA2HIP_FILTER_NSTATS
+# the int64 words of the stats of dada2hip_filter_open / _reads / _fastq / _fastq_paired, in order
+FILTER_STAGES = ("kept", "max_len", "trim_left", "trim_right", "trunc_q", "trunc_len", "min_len", "max_n", "min_q", "max_ee", "rm_phix",
+                 "rm_lowcomplex")   # a read's code indexes this
+FILTER_STATS = ("reads_in", "reads_kept") + tuple("dropped_" + s for s in FILTER_STAGES[1:]) + (
+    "table_keys", "table_in_lds", "upload_bytes", "upload_us", "scan_device_us", "ee_device_us", "kmers_device_us", "download_us",
+    "parse_us", "deflate_us", "write_us", "total_us", "open_inflate_us")
+
+
+class CFilterParams(C.Structure):
+    """dada2hip_filter_params"""
+    _fields_ = [("trunc_q", C.c_int32), ("trunc_len", C.c_int32), ("trim_left", C.c_int32), ("trim_right", C.c_int32),
+                ("max_len", C.c_int32), ("min_len", C.c_int32), ("max_n", C.c_int32), ("min_q", C.c_int32),
+                ("max_ee", C.c_double), ("rm_lowcomplex", C.c_double),
+                ("rm_phix", C.c_int32), ("min_matches", C.c_int32), ("non_overlapping", C.c_int32), ("kmer_size", C.c_int32),
+                ("qual_offset", C.c_int32), ("reserved", C.c_int32)]
 
 
 class CSampleInput(C.Structure):
@@ -295,6 +313,14 @@ def lib():
     L.dada2hip_species_hits_refs.restype = C.POINTER(C.c_int32)
     L.dada2hip_species_hits_free.argtypes = [vp]
     L.dada2hip_species_hits_free.restype = None
+    L.dada2hip_filter_open.argtypes = [cp, ip, ip, C.POINTER(vp), vp, cp, C.c_size_t]
+    L.dada2hip_filter_free.argtypes = [vp]
+    L.dada2hip_filter_free.restype = None
+    L.dada2hip_filter_reads.argtypes = [vp, C.c_int64, vp, vp, vp, C.POINTER(CFilterParams), vp, vp, vp, vp, vp, vp, vp, cp, C.c_size_t]
+    L.dada2hip_filter_fastq.argtypes = [vp, cp, cp, C.POINTER(CFilterParams), ip, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                        vp, cp, C.c_size_t]
+    L.dada2hip_filter_fastq_paired.argtypes = [vp, cp, cp, cp, cp, C.POINTER(CFilterParams), C.POINTER(CFilterParams), ip, C.c_int64,
+                                               C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp, cp, C.c_size_t]
     L.dada2hip_trim_cache.argtypes = []
     L.dada2hip_trim_cache.restype = None
     _lib = L

@@ -1005,6 +1005,305 @@ def add_species(taxtab, seqs, ref, colnames=None, allow_multiple=False, try_rc=F
     return out
 
 
+# ---- filterAndTrim (R/filter.R:402-1120, :1180-1275; src/filter.cpp) ----
+
+_FILTER_DEFAULTS = dict(trunc_q=2, trunc_len=0, trim_left=0, trim_right=0, max_len=float("inf"), min_len=20, max_n=0, min_q=0,
+                        max_ee=float("inf"), rm_lowcomplex=0)
+_FILTER_REFUSED = {"orient_fwd": "orient.fwd (it reorders the reads of a chunk, so its output depends on n)",
+                   "match_ids": "matchIDs", "id_sep": "id.sep", "id_field": "id.field", "window": "seqComplexity's window"}
+
+
+def _refuse_filter_args(kw):
+    for k, v in kw.items():
+        if k not in _FILTER_REFUSED:
+            raise TypeError(f"unexpected argument {k!r}")
+        if v is not None and v is not False:
+            raise NotImplementedError(f"{_FILTER_REFUSED[k]} is not supported by this library.")
+
+
+def filter_params(which=0, *, trunc_q=2, trunc_len=0, trim_left=0, trim_right=0, max_len=float("inf"), min_len=20, max_n=0, min_q=0,
+                  max_ee=float("inf"), rm_phix=False, rm_lowcomplex=0, min_matches=2, non_overlapping=True, kmer_size=0,
+                  quality_type=0):
+    """A dada2hip_filter_params.  The nine trimming arguments and rm_lowcomplex may be pairs (forward, reverse), as in
+    fastqPairedFilter (R/filter.R:890-906); ``which`` picks the direction.  max_len inf is "no limit"."""
+    def pick(v, name):
+        if isinstance(v, (list, tuple, np.ndarray)):
+            if len(v) not in (1, 2):
+                raise ValueError(f"Input variable {name} must be length 1 or 2 (Forward, Reverse).")
+            v = v[which if len(v) == 2 else 0]
+        return v
+    import math
+    ml = pick(max_len, "maxLen")
+    p = _lib.CFilterParams()
+    p.trunc_q, p.trunc_len = int(pick(trunc_q, "truncQ")), int(pick(trunc_len, "truncLen"))
+    p.trim_left, p.trim_right = int(pick(trim_left, "trimLeft")), int(pick(trim_right, "trimRight"))
+    p.max_len = 0 if (ml is None or math.isinf(ml)) else max(int(ml), 1) if ml >= 1 else -1
+    if p.max_len < 0:
+        raise ValueError("maxLen must be at least 1.")
+    p.min_len, p.max_n, p.min_q = int(pick(min_len, "minLen")), int(pick(max_n, "maxN")), int(pick(min_q, "minQ"))
+    p.max_ee = float(pick(max_ee, "maxEE"))
+    p.rm_lowcomplex = float(pick(rm_lowcomplex, "rm.lowcomplex"))
+    p.rm_phix, p.min_matches, p.non_overlapping = int(bool(rm_phix)), int(min_matches), int(bool(non_overlapping))
+    p.kmer_size, p.qual_offset = int(kmer_size), int(quality_type)
+    return p
+
+
+def _screen_sequence(phix):
+    """The screen's reference: a sequence of A/C/G/T, or the path of a FASTA file whose first record is taken."""
+    if phix is None or phix is False:
+        return None
+    if hasattr(phix, "__fspath__"):
+        phix = phix.__fspath__()
+    import os
+    phix = phix.decode() if isinstance(phix, bytes) else str(phix)
+    if not os.path.exists(phix):
+        if phix.isalpha():
+            return phix                                                    # (the library checks the letters)
+        raise FileNotFoundError(phix)
+    _, seqs = read_fasta(phix)
+    if not seqs:
+        raise ValueError("No sequence in the screen's reference file.")
+    return seqs[0]
+
+
+class FilterContext:
+    """The state of filterAndTrim that stays on ``device`` across files: the word table of the phiX screen (``phix``: the genome as
+    a string or the path of a FASTA file; the library ships none; None: no screen) and the expected-error tables."""
+
+    def __init__(self, phix=None, word_size: int = 16, device: int = 0):
+        self.ref = _screen_sequence(phix)
+        self.word_size, self.device = int(word_size), device
+        self._h = C.c_void_p()
+        st = np.zeros(_lib.FILTER_NSTATS, dtype=np.int64)
+        eb = C.create_string_buffer(_EB)
+        _lib.check(_lib.lib().dada2hip_filter_open(self.ref.encode() if self.ref is not None else None, self.word_size, device,
+                                                   C.byref(self._h), st.ctypes.data, eb, _EB), eb)
+        self.stats = {k: int(st[i]) for i, k in enumerate(_lib.FILTER_STATS)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().dada2hip_filter_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _blob(strs):
+    bs = [s if isinstance(s, bytes) else str(s).encode() for s in strs]
+    off = np.zeros(len(bs) + 1, dtype=np.int64)
+    if bs:
+        np.cumsum([len(b) for b in bs], out=off[1:])
+    return b"".join(bs), off
+
+
+def filter_reads(seqs, quals, ctx: FilterContext, params=None, *, kmers=False, stats: dict = None, **kw):
+    """dada2hip_filter_reads on reads in memory (``quals``: the quality strings as in the FASTQ file).  Returns a dict: ``code``
+    (0 kept, else the first stage failed, an index into _lib.FILTER_STAGES), ``window`` (n, 2: offset and length kept), ``ee``,
+    ``hits`` (n, 2: the screen's counts against the reference and its reverse complement) and, with ``kmers``, ``kmer_counts``
+    (n, 4^k) and ``complexity``.  ``params``: a filter_params(), or its keywords."""
+    p = params if params is not None else filter_params(**kw)
+    sb, off = _blob(seqs)
+    qb, qoff = _blob(quals)
+    if not np.array_equal(off, qoff):
+        raise ValueError("Every read needs as many quality characters as bases.")
+    n = len(off) - 1
+    k = p.kmer_size or 2
+    out = {"code": np.zeros(n, dtype=np.int32), "window": np.zeros((n, 2), dtype=np.int32), "ee": np.zeros(n, dtype=np.float64),
+           "hits": np.zeros((n, 2), dtype=np.int32)}
+    if kmers:
+        out["kmer_counts"] = np.zeros((n, 4 ** k), dtype=np.int32)
+        out["complexity"] = np.zeros(n, dtype=np.float64)
+    st = np.zeros(_lib.FILTER_NSTATS, dtype=np.int64)
+    eb = C.create_string_buffer(_EB)
+    _lib.check(_lib.lib().dada2hip_filter_reads(ctx._h, n, sb, qb, off.ctypes.data, C.byref(p), out["code"].ctypes.data,
+                                                out["window"].ctypes.data, out["ee"].ctypes.data, out["hits"].ctypes.data,
+                                                out["kmer_counts"].ctypes.data if kmers else None,
+                                                out["complexity"].ctypes.data if kmers else None, st.ctypes.data, eb, _EB), eb)
+    if stats is not None:
+        stats.update({k_: int(st[i]) for i, k_ in enumerate(_lib.FILTER_STATS)})
+    return out
+
+
+def _whole_read_params(**kw):
+    """Parameters under which every non-empty read is kept whole (the quality characters handed over are 'I')."""
+    return filter_params(trunc_q=-1, min_len=0, max_n=2 ** 31 - 1, quality_type=33, **kw)
+
+
+def match_ref(seqs, ref, word_size=16, non_overlapping=True, device: int = 0):
+    """C_matchRef (src/filter.cpp:7-32): per sequence the number of its windows of ``word_size`` that are words of the circular
+    ``ref``, counted greedily when ``non_overlapping`` (a hit at j makes j + word_size + 1 the next window tested)."""
+    seqs = [seqs] if isinstance(seqs, str) else [str(s) for s in seqs]
+    with FilterContext(ref, word_size, device) as ctx:
+        got = filter_reads(seqs, ["I" * len(s) for s in seqs], ctx, _whole_read_params(non_overlapping=non_overlapping))
+    return got["hits"][:, 0].copy()
+
+
+def is_phix(seqs, phix, word_size=16, min_matches=2, non_overlapping=True, device: int = 0):
+    """isPhiX (R/filter.R:1180-1187) against the genome ``phix`` (a string, a FASTA path or an open FilterContext): True where the
+    count against the genome or the count against its reverse complement reaches ``min_matches``."""
+    seqs = [seqs] if isinstance(seqs, str) else [str(s) for s in seqs]
+    ctx = phix if isinstance(phix, FilterContext) else FilterContext(phix, word_size, device)
+    try:
+        got = filter_reads(seqs, ["I" * len(s) for s in seqs], ctx, _whole_read_params(non_overlapping=non_overlapping))
+    finally:
+        if ctx is not phix:
+            ctx.close()
+    return (got["hits"] >= int(min_matches)).any(axis=1)
+
+
+def seq_complexity(seqs, kmer_size=2, window=None, device: int = 0):
+    """seqComplexity (R/filter.R:1248-1275) with window = NULL: the Shannon richness of the k-mers that are A/C/G/T only; NaN for
+    a sequence without one."""
+    if window is not None:
+        raise NotImplementedError("seqComplexity's window is not supported by this library.")
+    seqs = [seqs] if isinstance(seqs, str) else [str(s) for s in seqs]
+    with FilterContext(None, 16, device) as ctx:
+        got = filter_reads(seqs, ["I" * len(s) for s in seqs], ctx, _whole_read_params(kmer_size=kmer_size), kmers=True)
+    return got["complexity"]
+
+
+def _filter_ctx(rm_phix, ctx, device):
+    if ctx is not None:
+        return ctx, False
+    if rm_phix is True:
+        raise ValueError("rm_phix needs the genome (a sequence or the path of a FASTA file): the library ships no copy of it.")
+    return FilterContext(rm_phix if rm_phix else None, 16, device), True
+
+
+def fastq_filter(fn, fout, *, compress=True, n=10**6, quality_type=0, verbose=False, rm_phix=False, ctx: FilterContext = None,
+                 device: int = 0, stats: dict = None, min_matches=2, non_overlapping=True, kmer_size=0, **kw):
+    """fastqFilter (R/filter.R:613-730): (reads_in, reads_out).  ``rm_phix``: the genome (sequence or FASTA path), or True with a
+    ``ctx`` that holds it, or False."""
+    _refuse_filter_args({k: kw.pop(k) for k in list(kw) if k in _FILTER_REFUSED})
+    for k, v in kw.items():
+        if k not in _FILTER_DEFAULTS:
+            raise TypeError(f"unexpected argument {k!r}")
+        if isinstance(v, (list, tuple, np.ndarray)) and len(v) > 1:
+            raise ValueError("Filtering and trimming arguments should be of length 1 when processing single-end (rather than paired-end) data.")
+    c, own = _filter_ctx(rm_phix, ctx, device)
+    try:
+        p = filter_params(rm_phix=bool(rm_phix), min_matches=min_matches, non_overlapping=non_overlapping, kmer_size=kmer_size,
+                          quality_type=quality_type, **kw)
+        rin, rout = C.c_int64(), C.c_int64()
+        st = np.zeros(_lib.FILTER_NSTATS, dtype=np.int64)
+        eb = C.create_string_buffer(_EB)
+        _lib.check(_lib.lib().dada2hip_filter_fastq(c._h, str(fn).encode(), str(fout).encode(), C.byref(p), int(bool(compress)), int(n),
+                                                    C.byref(rin), C.byref(rout), st.ctypes.data, eb, _EB), eb)
+    finally:
+        if own:
+            c.close()
+    if stats is not None:
+        stats.update({k_: int(st[i]) for i, k_ in enumerate(_lib.FILTER_STATS)})
+    if verbose:
+        print(f"Read in {rin.value}, output {rout.value} ({round(rout.value * 100 / max(rin.value, 1), 1)}%) filtered sequences.")
+    if rout.value == 0 and verbose:
+        print(f"The filter removed all reads: {fout} not written.")
+    return rin.value, rout.value
+
+
+def fastq_paired_filter(fn, fout, *, compress=True, n=10**6, quality_type=0, verbose=False, rm_phix=False, ctx: FilterContext = None,
+                        device: int = 0, stats: dict = None, min_matches=2, non_overlapping=True, kmer_size=0, **kw):
+    """fastqPairedFilter (R/filter.R:878-1140): ``fn`` and ``fout`` are (forward, reverse); a pair is kept when both reads pass;
+    every trimming argument may be a pair."""
+    _refuse_filter_args({k: kw.pop(k) for k in list(kw) if k in _FILTER_REFUSED})
+    if isinstance(fn, str) or len(fn) != 2:
+        raise ValueError("Two paired input file names required.")
+    if isinstance(fout, str) or len(fout) != 2:
+        raise ValueError("Two paired output file names required.")
+    for k in kw:
+        if k not in _FILTER_DEFAULTS:
+            raise TypeError(f"unexpected argument {k!r}")
+    c, own = _filter_ctx(rm_phix, ctx, device)
+    try:
+        ps = [filter_params(w, rm_phix=bool(rm_phix), min_matches=min_matches, non_overlapping=non_overlapping, kmer_size=kmer_size,
+                            quality_type=quality_type, **kw) for w in (0, 1)]
+        rin, rout = C.c_int64(), C.c_int64()
+        st = np.zeros(_lib.FILTER_NSTATS, dtype=np.int64)
+        eb = C.create_string_buffer(_EB)
+        _lib.check(_lib.lib().dada2hip_filter_fastq_paired(c._h, str(fn[0]).encode(), str(fn[1]).encode(), str(fout[0]).encode(),
+                                                           str(fout[1]).encode(), C.byref(ps[0]), C.byref(ps[1]), int(bool(compress)),
+                                                           int(n), C.byref(rin), C.byref(rout), st.ctypes.data, eb, _EB), eb)
+    finally:
+        if own:
+            c.close()
+    if stats is not None:
+        stats.update({k_: int(st[i]) for i, k_ in enumerate(_lib.FILTER_STATS)})
+    if verbose:
+        print(f"Read in {rin.value} paired-sequences, output {rout.value} ({round(rout.value * 100 / max(rin.value, 1), 1)}%) filtered paired-sequences.")
+    return rin.value, rout.value
+
+
+def filter_and_trim(fwd, filt, rev=None, filt_rev=None, *, compress=True, trunc_q=2, trunc_len=0, trim_left=0, trim_right=0,
+                    max_len=float("inf"), min_len=20, max_n=0, min_q=0, max_ee=float("inf"), rm_phix=False, rm_lowcomplex=0, n=10**5,
+                    quality_type=0, device: int = 0, verbose=False, ctx: FilterContext = None, **kw):
+    """filterAndTrim (R/filter.R:402-497) over one file or lists of files: returns (an (nfiles, 2) int64 array of reads.in /
+    reads.out, the row names basename(fwd)).  ``rm_phix``: the phiX genome as a sequence or the path of a FASTA file (the library
+    ships no copy), or False.  Output directories are created; duplicate output paths and outputs equal to an input are
+    refused; a file from which nothing passes is not written."""
+    import os
+    _refuse_filter_args(kw)
+    aslist = lambda x: [os.fspath(x)] if (isinstance(x, (str, bytes)) or hasattr(x, "__fspath__")) else [os.fspath(y) for y in x]   # noqa: E731
+    fwd, filt = aslist(fwd), aslist(filt)
+    if not all(os.path.exists(f) for f in fwd):
+        raise ValueError("Some input files do not exist.")
+    if len(filt) == 1 and len(fwd) > 1:
+        filt = [os.path.join(filt[0], os.path.basename(f)) for f in fwd]
+    if len(fwd) != len(filt):
+        raise ValueError("Every input file must have a corresponding output file.")
+    paired = rev is not None
+    if paired:
+        if filt_rev is None:
+            raise ValueError("Output files for the reverse reads are required.")
+        rev, filt_rev = aslist(rev), aslist(filt_rev)
+        if not all(os.path.exists(f) for f in rev):
+            raise ValueError("Some input files (rev) do not exist.")
+        if len(rev) != len(fwd):
+            raise ValueError("Paired forward and reverse input files must correspond.")
+        if len(filt_rev) == 1 and len(rev) > 1:
+            filt_rev = [os.path.join(filt_rev[0], os.path.basename(f)) for f in rev]
+        if len(rev) != len(filt_rev):
+            raise ValueError("Every input file (rev) must have a corresponding output file (filt.rev).")
+    outs = [os.path.abspath(f) for f in filt + (filt_rev if paired else [])]
+    ins = [os.path.realpath(f) for f in fwd + (rev if paired else [])]
+    for o in outs:
+        if os.path.dirname(o):
+            os.makedirs(os.path.dirname(o), exist_ok=True)
+    outs = [os.path.realpath(o) for o in outs]
+    if len(set(outs)) != len(outs):
+        raise ValueError("All output files must be distinct.")
+    if set(outs) & set(ins):
+        raise ValueError("Output files must be distinct from the input files.")
+    args = dict(trunc_q=trunc_q, trunc_len=trunc_len, trim_left=trim_left, trim_right=trim_right, max_len=max_len, min_len=min_len,
+                max_n=max_n, min_q=min_q, max_ee=max_ee, rm_lowcomplex=rm_lowcomplex)
+    c, own = _filter_ctx(rm_phix, ctx, device)
+    rval = np.zeros((len(fwd), 2), dtype=np.int64)
+    try:
+        for i in range(len(fwd)):
+            if paired:
+                rval[i] = fastq_paired_filter((fwd[i], rev[i]), (filt[i], filt_rev[i]), compress=compress, n=n, quality_type=quality_type,
+                                              verbose=verbose, rm_phix=bool(rm_phix), ctx=c, **args)
+            else:
+                rval[i] = fastq_filter(fwd[i], filt[i], compress=compress, n=n, quality_type=quality_type, verbose=verbose,
+                                       rm_phix=bool(rm_phix), ctx=c, **args)
+    finally:
+        if own:
+            c.close()
+    if len(fwd) and (rval[:, 1] == 0).all():
+        import warnings
+        warnings.warn("No reads passed the filter. Please revisit your filtering parameters.")
+    return rval, [os.path.basename(f) for f in fwd]
+
+
 def calc_pA_device(reads, E, prior, device: int = 0):
     """calc_pA (src/pval.cpp:44-64) evaluated by the device kernel."""
     L = _lib.lib()

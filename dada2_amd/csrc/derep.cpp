@@ -16,6 +16,7 @@
 #include <condition_variable>
 #include <cstring>
 #include <deque>
+#include <future>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -576,6 +577,300 @@ int dada2hip_sample_from_derep(const dada2hip_derep *d, const uint8_t *priors, i
   if (!d) { set_err(errbuf, errlen, "dada2hip: no derep object"); return DADA2HIP_ERR_INPUT; }
   return dada2hip_sample_create((int32_t)d->seq_ptrs.size(), d->seq_ptrs.data(), d->abund.data(), priors, d->quals.get(), d->maxlen, device,
                                 out, errbuf, errlen);
+}
+
+}  // extern "C"
+
+// ---- filterAndTrim's file level (R/filter.R:613-730 fastqFilter, :878-1140 fastqPairedFilter) -------------------------------------
+// The per-read verdicts are dada2hip_filter_reads' (filter_host.h, filter.inc.hip); here are the reader, the chunks, the paired
+// AND and the writer.  A chunk's records are copied out of the reader's lines into three blobs (header lines, sequences,
+// qualities) and the offsets the kernels take; the kept records are laid out as ShortRead's writeFastq does (`@id`, the bases, a
+// bare `+`, the qualities) by the host pool and, with compress, deflated in pieces over the pool, every piece a gzip member of
+// its own (concatenated members are one valid .gz; a single deflate stream on one thread would be the whole run).
+namespace {
+
+struct FqSource {
+  std::string path;
+  gzFile f = nullptr;
+  FILE *plain = nullptr;
+  std::unique_ptr<LineReader> in;
+  bool at_end = false;
+  ~FqSource() {
+    in.reset();                                                 // (the reader thread joins before the files close)
+    if (f) gzclose(f);
+    if (plain) fclose(plain);
+  }
+  bool open(const char *p, std::string &err) {
+    path = p;
+    f = gzopen(p, "rb");
+    if (!f) { err = "Some input files do not exist."; return false; }
+    gzbuffer(f, 1 << 20);
+    plain = gzdirect(f) ? fopen(p, "rb") : nullptr;
+    Bytes whole;
+    int have_whole = 0;
+    if (!plain && !d2::knobs().derep_zlib) {
+      std::string why;
+      have_whole = inflate_whole(p, whole, why);
+      if (have_whole < 0) { err = "dada2hip: error reading " + path + ": " + why; return false; }
+    }
+    in.reset(have_whole > 0 ? new LineReader(std::move(whole)) : new LineReader(f, plain));
+    return true;
+  }
+};
+
+struct FqChunk {
+  Bytes hdr, seq, qual;
+  std::vector<int64_t> hoff, off;
+  int64_t n = 0;
+  void clear() { hdr.clear(); seq.clear(); qual.clear(); hoff.assign(1, 0); off.assign(1, 0); n = 0; }
+};
+
+void bytes_append(Bytes &b, const char *p, size_t n) {
+  const size_t at = b.size();
+  if (b.capacity() < at + n) b.reserve(std::max(at + n, b.capacity() * 2));
+  b.resize(at + n);
+  memcpy(b.data() + at, p, n);
+}
+
+// up to `limit` records into c; false on a malformed record or a damaged stream (err)
+bool fq_read_chunk(FqSource &S, int64_t limit, FqChunk &c, std::string &err) {
+  c.clear();
+  LineReader &in = *S.in;
+  const char *hp, *sp, *pp, *qp;
+  size_t hn, sn, pn, qn;
+  while (c.n < limit && !S.at_end) {
+    if (!in.next(&hp, &hn)) { S.at_end = true; break; }
+    if (hn == 0) continue;
+    const bool ok = hp[0] == '@' && in.next(&sp, &sn) && in.next(&pp, &pn) && pn > 0 && pp[0] == '+' && in.next(&qp, &qn) && qn == sn;
+    if (!ok) {
+      const std::string ze = in.error();
+      err = !ze.empty() ? "dada2hip: error reading " + S.path + ": " + ze : std::string("dada2hip: malformed FASTQ record");
+      return false;
+    }
+    // (a refill moves the window: each line is copied before the next one is asked for only where it has to be - the four lines
+    // of a record stay valid until release())
+    bytes_append(c.hdr, hp, hn); bytes_append(c.seq, sp, sn); bytes_append(c.qual, qp, qn);
+    c.hoff.push_back((int64_t)c.hdr.size()); c.off.push_back((int64_t)c.seq.size());
+    c.n++;
+    if ((c.n & 4095) == 0) in.release();
+  }
+  in.release();
+  if (S.at_end) {
+    const std::string ze = in.error();
+    if (!ze.empty()) { err = "dada2hip: error reading " + S.path + ": " + ze; return false; }
+  }
+  return true;
+}
+
+int fq_auto_offset(const FqChunk &c) {
+  int m = 255;
+  for (char ch : c.qual) m = std::min(m, (int)(unsigned char)ch);
+  return m < 59 ? 33 : 64;
+}
+
+struct FqWriter {
+  std::string path;
+  FILE *fp = nullptr;
+  bool compress = false;
+  int64_t us_deflate = 0, us_write = 0;
+  ~FqWriter() { if (fp) fclose(fp); }
+  // the records of c with keep[i] != 0, cut to win[2 i], win[2 i + 1]
+  bool put(const FqChunk &c, const std::vector<uint8_t> &keep, const std::vector<int32_t> &win, std::string &err) {
+    using wclk = std::chrono::steady_clock;
+    auto us_since = [](wclk::time_point t) { return (int64_t)std::chrono::duration<double, std::micro>(wclk::now() - t).count(); };
+    auto t0 = wclk::now();
+    std::vector<size_t> at((size_t)c.n + 1, 0);
+    for (int64_t i = 0; i < c.n; i++)
+      at[i + 1] = at[i] + (keep[i] ? (size_t)(c.hoff[i + 1] - c.hoff[i]) + 2 * (size_t)win[2 * i + 1] + 5 : 0);
+    if (at[c.n] == 0) return true;
+    Bytes text(at[c.n]);
+    d2::parallel_for((size_t)c.n, 1024, [&](size_t i0, size_t i1) {
+      for (size_t i = i0; i < i1; i++) {
+        if (!keep[i]) continue;
+        char *o = text.data() + at[i];
+        const size_t hl = (size_t)(c.hoff[i + 1] - c.hoff[i]), wl = (size_t)win[2 * i + 1], wo = (size_t)win[2 * i];
+        memcpy(o, c.hdr.data() + c.hoff[i], hl); o += hl; *o++ = '\n';
+        memcpy(o, c.seq.data() + c.off[i] + wo, wl); o += wl; *o++ = '\n'; *o++ = '+'; *o++ = '\n';
+        memcpy(o, c.qual.data() + c.off[i] + wo, wl); o += wl; *o++ = '\n';
+      }
+    });
+    if (!fp) {
+      fp = fopen(path.c_str(), "wb");
+      if (!fp) { err = "dada2hip: cannot write " + path; return false; }
+    }
+    if (!compress) {
+      if (fwrite(text.data(), 1, text.size(), fp) != text.size()) { err = "dada2hip: error writing " + path; return false; }
+      us_write += us_since(t0);
+      return true;
+    }
+    const size_t PIECE = (size_t)1 << 20, np = (text.size() + PIECE - 1) / PIECE;
+    std::vector<Bytes> z(np);
+    std::vector<int> zrc(np, Z_OK);
+    d2::parallel_for(np, 1, [&](size_t p0, size_t p1) {
+      for (size_t p = p0; p < p1; p++) {
+        const size_t lo = p * PIECE, len = std::min(PIECE, text.size() - lo);
+        z_stream zs;
+        memset(&zs, 0, sizeof zs);
+        if (deflateInit2(&zs, Z_DEFAULT_COMPRESSION, Z_DEFLATED, 15 + 16, 8, Z_DEFAULT_STRATEGY) != Z_OK) { zrc[p] = Z_MEM_ERROR; continue; }
+        z[p].resize(deflateBound(&zs, (uLong)len) + 32);
+        zs.next_in = (Bytef *)(text.data() + lo); zs.avail_in = (uInt)len;
+        zs.next_out = (Bytef *)z[p].data(); zs.avail_out = (uInt)z[p].size();
+        const int r = deflate(&zs, Z_FINISH);
+        if (r != Z_STREAM_END) zrc[p] = r == Z_OK ? Z_BUF_ERROR : r;
+        z[p].resize(zs.total_out);
+        deflateEnd(&zs);
+      }
+    });
+    us_deflate += us_since(t0);
+    t0 = wclk::now();
+    for (size_t p = 0; p < np; p++) {
+      if (zrc[p] != Z_OK) { err = "dada2hip: deflate failed while writing " + path; return false; }
+      if (fwrite(z[p].data(), 1, z[p].size(), fp) != z[p].size()) { err = "dada2hip: error writing " + path; return false; }
+    }
+    us_write += us_since(t0);
+    return true;
+  }
+  bool finish(std::string &err) {
+    if (fp) { const int r = fclose(fp); fp = nullptr; if (r != 0) { err = "dada2hip: error writing " + path; return false; } }
+    return true;
+  }
+};
+
+// FS_* of filter_host.h: the words of a call's stats that add up over chunks, and the file level's own
+enum { FQ_US_PARSE = 21, FQ_US_DEFLATE = 22, FQ_US_WRITE = 23, FQ_US_TOTAL = 24, FQ_US_INFLATE = 25 };
+void fq_add_stats(int64_t *tot, const int64_t *st) {
+  for (int i = 0; i < DADA2HIP_FILTER_NSTATS; i++)
+    if (i == 13 || i == 14) tot[i] = st[i]; else if (i != FQ_US_TOTAL) tot[i] += st[i];
+}
+
+int filter_files_body(dada2hip_filter *ctx, int nfile, const char *const *in, const char *const *out,
+                      const dada2hip_filter_params *const *params, int32_t compress, int64_t chunk_reads, int64_t *reads_in,
+                      int64_t *reads_out, int64_t *stats, char *errbuf, size_t errlen) {
+  using fclk = std::chrono::steady_clock;
+  auto us_since = [](fclk::time_point t) { return (int64_t)std::chrono::duration<double, std::micro>(fclk::now() - t).count(); };
+  const auto t_call = fclk::now();
+  if (reads_in) *reads_in = 0;
+  if (reads_out) *reads_out = 0;
+  for (int k = 0; k < nfile; k++)
+    if (!in[k] || !out[k] || !params[k]) { set_err(errbuf, errlen, "File paths must be provided in character format."); return DADA2HIP_ERR_INPUT; }
+  for (int a = 0; a < nfile; a++) {                             // :627, :887
+    for (int b = 0; b < nfile; b++)
+      if (strcmp(in[a], out[b]) == 0) {
+        set_err(errbuf, errlen, nfile == 1 ? "The output and input files must be different." : "The output and input file names must be different.");
+        return DADA2HIP_ERR_INPUT;
+      }
+    for (int b = 0; b < a; b++)
+      if (strcmp(out[a], out[b]) == 0 || strcmp(in[a], in[b]) == 0) { set_err(errbuf, errlen, "The output and input file names must be different."); return DADA2HIP_ERR_INPUT; }
+  }
+  if (chunk_reads <= 0) chunk_reads = 100000;                   // filterAndTrim(n = 1e5)
+  d2::knobs_reload();
+  FqSource src[2];
+  FqWriter wr[2];
+  FqChunk chunks[2][2];                                         // [slot][file]: the parser fills one slot while the other is filtered and written
+  dada2hip_filter_params P[2];
+  std::string err;
+  int64_t tot[DADA2HIP_FILTER_NSTATS] = {0}, st[DADA2HIP_FILTER_NSTATS];
+  for (int k = 0; k < nfile; k++) {
+    const auto t_open = fclk::now();                            // (a .gz that libdeflate takes is inflated HERE, in one go)
+    if (!src[k].open(in[k], err)) { set_err(errbuf, errlen, err.c_str()); return DADA2HIP_ERR_INPUT; }
+    tot[FQ_US_INFLATE] += us_since(t_open);
+    P[k] = *params[k];
+    wr[k].path = out[k]; wr[k].compress = compress != 0;
+  }
+  for (int k = 0; k < nfile; k++) (void)remove(out[k]);         // :634-640 (writeFastq does not overwrite)
+  int64_t nin = 0, nout = 0;
+  std::vector<int32_t> code[2], win[2];
+  std::vector<uint8_t> keep;
+  int rc = DADA2HIP_OK;
+  struct Parsed { bool ok; std::string err; int64_t us; };
+  auto parse = [&](int slot) {
+    const auto t_parse = fclk::now();
+    Parsed r{true, std::string(), 0};
+    for (int k = 0; k < nfile && r.ok; k++) r.ok = fq_read_chunk(src[k], chunk_reads, chunks[slot][k], r.err);
+    r.us = us_since(t_parse);
+    return r;
+  };
+  std::future<Parsed> ahead = std::async(std::launch::async, parse, 0);
+  for (int slot = 0;; slot ^= 1) {
+    const bool first = nin == 0;
+    const Parsed got = ahead.get();
+    tot[FQ_US_PARSE] += got.us;
+    if (!got.ok) { set_err(errbuf, errlen, got.err.c_str()); rc = DADA2HIP_ERR_INPUT; break; }
+    FqChunk *ch = chunks[slot];
+    if (nfile == 2 && ch[0].n != ch[1].n) {                     // :966
+      set_err(errbuf, errlen, ("Mismatched forward and reverse sequence files: " + std::to_string(ch[0].n) + ", " + std::to_string(ch[1].n) + ".").c_str());
+      rc = DADA2HIP_ERR_INPUT;
+      break;
+    }
+    const int64_t n = ch[0].n;
+    if (n == 0) break;
+    ahead = std::async(std::launch::async, parse, slot ^ 1);   // the next chunk is read and parsed under this one's kernels and deflate
+    nin += n;
+    keep.assign((size_t)n, 1);
+    for (int k = 0; k < nfile && rc == DADA2HIP_OK; k++) {
+      if (first && P[k].qual_offset == 0) P[k].qual_offset = fq_auto_offset(ch[k]);
+      code[k].resize((size_t)n); win[k].resize(2 * (size_t)n);
+      rc = dada2hip_filter_reads(ctx, n, ch[k].seq.data(), ch[k].qual.data(), ch[k].off.data(), &P[k], code[k].data(), win[k].data(),
+                                 nullptr, nullptr, nullptr, nullptr, st, errbuf, errlen);
+      if (rc != DADA2HIP_OK) break;
+      if (k == 0) fq_add_stats(tot, st);
+      else for (int i = 15; i <= 20; i++) tot[i] += st[i];     // (the verdict counts are the forward reads'; the clocks are both files')
+      for (int64_t i = 0; i < n; i++) if (code[k][i] != 0) keep[i] = 0;
+    }
+    if (rc != DADA2HIP_OK) break;
+    for (int64_t i = 0; i < n; i++) nout += keep[i];
+    for (int k = 0; k < nfile && rc == DADA2HIP_OK; k++)
+      if (!wr[k].put(ch[k], keep, win[k], err)) { set_err(errbuf, errlen, err.c_str()); rc = DADA2HIP_ERR_RUNTIME; }
+    if (rc != DADA2HIP_OK) break;
+  }
+  if (ahead.valid()) ahead.wait();                              // (a run that stops early still waits for its parser)
+  for (int k = 0; k < nfile; k++) {
+    if (!wr[k].finish(err) && rc == DADA2HIP_OK) { set_err(errbuf, errlen, err.c_str()); rc = DADA2HIP_ERR_RUNTIME; }
+    tot[FQ_US_DEFLATE] += wr[k].us_deflate; tot[FQ_US_WRITE] += wr[k].us_write;
+  }
+  if (rc != DADA2HIP_OK) {                                      // nothing half written is left behind
+    for (int k = 0; k < nfile; k++) (void)remove(out[k]);
+    return rc;
+  }
+  tot[0] = nin; tot[1] = nout; tot[FQ_US_TOTAL] = us_since(t_call);
+  if (reads_in) *reads_in = nin;
+  if (reads_out) *reads_out = nout;
+  if (stats) memcpy(stats, tot, sizeof tot);
+  return DADA2HIP_OK;
+}
+
+template <typename F> int filter_files_guarded(char *errbuf, size_t errlen, F &&f) {
+  try {
+    return f();
+  } catch (const std::bad_alloc &) {
+    set_err(errbuf, errlen, "dada2hip: out of host memory during filtering");
+  } catch (const std::exception &e) {
+    set_err(errbuf, errlen, (std::string("dada2hip: ") + e.what()).c_str());
+  } catch (...) {
+    set_err(errbuf, errlen, "dada2hip: unknown error during filtering");
+  }
+  return DADA2HIP_ERR_RUNTIME;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dada2hip_filter_fastq(dada2hip_filter *ctx, const char *in, const char *out, const dada2hip_filter_params *params, int32_t compress,
+                          int64_t chunk_reads, int64_t *reads_in, int64_t *reads_out, int64_t *stats, char *errbuf, size_t errlen) {
+  return filter_files_guarded(errbuf, errlen, [&] {
+    return filter_files_body(ctx, 1, &in, &out, &params, compress, chunk_reads, reads_in, reads_out, stats, errbuf, errlen);
+  });
+}
+
+int dada2hip_filter_fastq_paired(dada2hip_filter *ctx, const char *in_f, const char *in_r, const char *out_f, const char *out_r,
+                                 const dada2hip_filter_params *params_f, const dada2hip_filter_params *params_r, int32_t compress,
+                                 int64_t chunk_reads, int64_t *reads_in, int64_t *reads_out, int64_t *stats, char *errbuf, size_t errlen) {
+  const char *in[2] = {in_f, in_r}, *out[2] = {out_f, out_r};
+  const dada2hip_filter_params *params[2] = {params_f, params_r};
+  return filter_files_guarded(errbuf, errlen, [&] {
+    return filter_files_body(ctx, 2, in, out, params, compress, chunk_reads, reads_in, reads_out, stats, errbuf, errlen);
+  });
 }
 
 }  // extern "C"

@@ -620,6 +620,33 @@ void launch_species_seed(const SpeciesRefs &R, int r0, int r1, const SpeciesKeys
                          unsigned long long cap, unsigned long long *d_counters, hipStream_t st);
 void launch_species_verify(const SpeciesRefs &R, const SpeciesKeys &K, const SpCand *d_cand, unsigned long long ncand,
                            unsigned long long *d_hits, unsigned long long hit_cap, unsigned long long *d_counters, hipStream_t st);
+// filterAndTrim (filter.inc.hip).  A batch is n reads: the bytes of read r are seq / qual[off[r] .. off[r + 1]).  The screen's word
+// set is ONE sorted array of the distinct keys of both strands with a byte of flags beside it (bit 0: the word occurs in the
+// reference, bit 1: in its reverse complement).  A key is a window's two bit planes side by side: bit t of the low half is bit 0
+// of base t's code (A C G T = 0 1 2 3), bit t of the high half is bit 1 of it - the form a lane gets from three ballots with no
+// bit interleave.  in_lds: the table fits the block's LDS (9 bytes per key); otherwise the search runs over global memory.
+constexpr int FT_THREADS = 1024;              // 16 waves share one copy of the table; a wave owns a read
+constexpr int FT_LDS_MAX = 144 * 1024;        // of the CU's 160 KiB
+struct FilterTable {
+  const unsigned long long *keys;
+  const uint8_t *flags;
+  int nkeys, word_size;
+};
+// the stages of R/filter.R:659-706 with the host's arithmetic done: skip = start - 1, cut_char = truncQ + offset (as a quality
+// CHARACTER), trunc_end = truncLen - start + 1 or 0 for none, minq_char = minQ + offset
+struct FilterArgs {
+  int max_len, skip, trim_right, cut_char, trunc_end, min_len, max_n, minq_on, minq_char, ee_on, rm_phix, min_matches, non_overlapping;
+  double max_ee;
+};
+struct FilterOut { int32_t code, off, len, nother, minq, hits_f, hits_r, pad; double ee; };
+void launch_filter_scan(const FilterTable &T, const FilterArgs &A, int n, const uint8_t *d_seq, const uint8_t *d_qual,
+                        const long long *d_off, FilterOut *d_out, hipStream_t st);
+// the in-order fp64 sum of ee_tab[quality character] over each kept window (C_matrixEE), then stages 9 and 10
+void launch_filter_ee(const FilterArgs &A, int n, const uint8_t *d_qual, const long long *d_off, const double *d_ee_tab,
+                      FilterOut *d_out, hipStream_t st);
+// counts[r][4^k]: the k-mers of the kept window that are A/C/G/T only, first letter most significant (oligonucleotideFrequency's order)
+void launch_filter_kmers(int n, int k, const uint8_t *d_seq, const long long *d_off, const FilterOut *d_out, int32_t *d_counts,
+                         hipStream_t st);
 void launch_calc_pA(int n, const int32_t *d_reads, const double *d_E, const uint8_t *d_prior, double *d_out,
                     hipStream_t st);
 

@@ -22,6 +22,8 @@
  *   dada2hip_taxonomy_*     <- C_assign_taxonomy2() src/taxonomy.cpp:206-338  (`_dada2_C_assign_taxonomy2`; R/taxonomy.R:135), split into
  *                              the model (:219-270, built once, resident in HBM) and the classification of queries (:113-200)
  *   dada2hip_derep_*        <- derepFastq() / qtables2()  R/sequenceIO.R:45-124, :150-183 (host-side C++, zlib)
+ *   dada2hip_filter_*       <- filterAndTrim() / fastqFilter() / fastqPairedFilter() / isPhiX() / seqComplexity()  R/filter.R:402-1275 on
+ *                              C_matchRef / C_matrixEE (src/filter.cpp:7-49)
  *
  * Conventions: plain C, no exceptions cross the boundary.  Every call returns 0 on success or a
  * non-zero code with a NUL-terminated message in `errbuf` (the reference's Rcpp::stop texts are
@@ -43,7 +45,7 @@
  *   DADA2HIP_NW_KERNEL=lane|coop|wide  force one aligner family;  DADA2HIP_AD_HOMO=0  homopolymer gaps on the lane kernels
  *   DADA2HIP_WAIT=block, DADA2HIP_WAIT_TIMEOUT_S=<s>   sleep instead of spin while waiting; bound of every device wait
  *   DADA2HIP_HOST_THREADS=<n>, DADA2HIP_ALLOC_CACHE=0, DADA2HIP_ALLOC_CACHE_GB=<n>   marshalling pool, allocation cache
- *   DADA2HIP_DEREP_INFLATE=zlib        dada2hip_derep_fastq: .gz files through zlib's streaming inflate even where libdeflate is installed
+ *   DADA2HIP_DEREP_INFLATE=zlib        dada2hip_derep_fastq, dada2hip_filter_fastq: .gz files through zlib's streaming inflate even where libdeflate is installed
  *   DADA2HIP_COLLAPSE_BATCH=<n>        dada2hip_collapse_nomismatch: queries per batch (default 0 = automatic)
  *   DADA2HIP_COLLAPSE_SCAN=0           ... every screened pair is aligned (the bound of the diagonal scan is not used)
  *   DADA2HIP_COLLAPSE_JOIN=0           ... every (query, ref) pair is scanned (no prefix-key join)
@@ -474,6 +476,66 @@ int dada2hip_species_match(const dada2hip_species *m, int32_t nseq, const char *
 const int64_t *dada2hip_species_hits_offsets(const dada2hip_species_hits *h);   /* nseq + 1 */
 const int32_t *dada2hip_species_hits_refs(const dada2hip_species_hits *h);      /* 0-based, ascending per query */
 void dada2hip_species_hits_free(dada2hip_species_hits *h);
+
+/* ---- filterAndTrim: read filtering and the phiX screen (R/filter.R:402-1120, src/filter.cpp) ----------------------------------
+ * A read is its sequence bytes and its quality bytes.  The stages run in fastqFilter's order (R/filter.R:659-706), with
+ * start = max(1, trim_left + 1); a read reports the FIRST stage it fails as its code:
+ *   1 max_len (> 0: raw width <= max_len)      2 trim_left (width >= start, then start - 1 bases dropped)
+ *   3 trim_right (> 0: width > trim_right, then that many dropped from the end)
+ *   4 trunc_q (cut at the first quality <= trunc_q; a read left with nothing is dropped)
+ *   5 trunc_len (>= start: width >= trunc_len - start + 1, then cut to it)          6 min_len (width >= min_len)
+ *   7 max_n (letters other than upper-case A/C/G/T <= max_n)     8 min_q (only if min_q > trunc_q: min(q) > min_q, strict)
+ *   9 max_ee (only if finite: the in-order fp64 sum of pow(10.0, -q / 10.0), C_matrixEE's bits, <= max_ee)
+ *  10 rm_phix (isPhiX: C_matchRef's count against the reference or the count against its reverse complement >= min_matches;
+ *     the counts are never summed; with non_overlapping a hit at window j makes j + word_size + 1 the next window tested;
+ *     a window with a letter other than upper-case A/C/G/T matches nothing; the reference is circular)
+ *  11 rm_lowcomplex (> 0: seqComplexity(read, kmer_size) >= rm_lowcomplex; a read with no valid k-mer is dropped)
+ * and 0 when it is kept.  qual_offset is 33, 64 or 0 = Auto (dada2hip_derep_fastq's rule: the smallest quality character of the
+ * call - of the first chunk, for a file - below ';' means 33, otherwise 64).
+ *
+ * dada2hip_filter_open builds the screen's word table from `ref` (upper-case A/C/G/T only, else DADA2HIP_ERR_UNSUPPORTED; shorter
+ * than word_size: DADA2HIP_ERR_INPUT; word_size outside 1..32: DADA2HIP_ERR_UNSUPPORTED) and keeps it on `device`.  The library
+ * ships no reference sequence.  ref == NULL: a context without a screen (rm_phix != 0 is then DADA2HIP_ERR_INPUT).
+ * dada2hip_filter_reads: n reads, read r being seq / qual[offsets[r] .. offsets[r + 1]).  Outputs (each optional): code[n];
+ * window[2 r], [2 r + 1] the kept window's offset and length inside the read (length 0 for codes 1-6); ee[n] (0 for codes 1-6);
+ * hits[2 r], [2 r + 1] the two counts of the screen; kmer_counts[r * 4^k + bin] the k-mers of the kept window that are A/C/G/T
+ * only, first letter most significant; complexity[n] = exp(sum(-y log y)) over the bins with y > 0, in bin order, by the host's
+ * libm (NaN without a valid k-mer).  kmer_size 0 means 2; outside 0..4: DADA2HIP_ERR_UNSUPPORTED.
+ * dada2hip_filter_fastq filters a FASTQ file (plain or gzip) into `out` in chunks of chunk_reads records (<= 0: 100 000):
+ * records as `@id\nseq\n+\nqual\n`, ids unchanged, input order; compress != 0: every chunk is deflated in pieces over the host
+ * pool, each piece a gzip member of its own.  in == out is DADA2HIP_ERR_INPUT ("The output and input files must be different.").
+ * An existing `out` is removed first; when nothing passes no file is left (:724-727).  dada2hip_filter_fastq_paired keeps a pair
+ * when both reads pass their own parameters; files of unequal read counts are DADA2HIP_ERR_INPUT ("Mismatched forward and
+ * reverse sequence files: ...").  A truncated or corrupt input is a read error, as in dada2hip_derep_fastq.
+ * stats (optional, DADA2HIP_FILTER_NSTATS int64 words): [0] reads in, [1] reads kept, [2..12] reads dropped at stage 1..11,
+ * [13] keys in the word table, [14] 1 when the table is searched in LDS, [15] bytes copied to the device, [16] host
+ * microseconds of the upload, [17] device microseconds of the scan kernel, [18] of the EE kernel, [19] of the k-mer kernel,
+ * [20] host microseconds of the download, [21] of parsing (on a thread of its own, under the previous chunk's work), [22] of
+ * deflate, [23] of writing, [24] of the whole call, [25] of opening the inputs (a gzip file that libdeflate takes is inflated
+ * there, in one go). */
+#define DADA2HIP_FILTER_NSTATS 32
+typedef struct dada2hip_filter dada2hip_filter;
+typedef struct dada2hip_filter_params {
+  int32_t trunc_q, trunc_len, trim_left, trim_right;
+  int32_t max_len;                 /* <= 0: no limit (maxLen = Inf) */
+  int32_t min_len, max_n, min_q;
+  double max_ee;                   /* not finite: not applied */
+  double rm_lowcomplex;            /* <= 0: not applied */
+  int32_t rm_phix, min_matches, non_overlapping, kmer_size, qual_offset, reserved;
+} dada2hip_filter_params;
+int dada2hip_filter_open(const char *ref, int32_t word_size, int32_t device, dada2hip_filter **out, int64_t *stats, char *errbuf,
+                         size_t errlen);
+void dada2hip_filter_free(dada2hip_filter *ctx);
+int dada2hip_filter_reads(dada2hip_filter *ctx, int64_t n, const char *seq, const char *qual, const int64_t *offsets,
+                          const dada2hip_filter_params *params, int32_t *code, int32_t *window, double *ee, int32_t *hits,
+                          int32_t *kmer_counts, double *complexity, int64_t *stats, char *errbuf, size_t errlen);
+int dada2hip_filter_fastq(dada2hip_filter *ctx, const char *in, const char *out, const dada2hip_filter_params *params,
+                          int32_t compress, int64_t chunk_reads, int64_t *reads_in, int64_t *reads_out, int64_t *stats,
+                          char *errbuf, size_t errlen);
+int dada2hip_filter_fastq_paired(dada2hip_filter *ctx, const char *in_f, const char *in_r, const char *out_f, const char *out_r,
+                                 const dada2hip_filter_params *params_f, const dada2hip_filter_params *params_r, int32_t compress,
+                                 int64_t chunk_reads, int64_t *reads_in, int64_t *reads_out, int64_t *stats, char *errbuf,
+                                 size_t errlen);
 
 /* One b_compare round exposed for kernel-level parity tests and for bench.py's roofline leg:
  * compares every unique of `s` against unique `centre` exactly as CompareParallel does

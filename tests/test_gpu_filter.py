@@ -1,0 +1,23 @@
+"""filterAndTrim on the MI355X (-m gpu): dada2hip_filter_open / _reads / _fastq / _fastq_paired against the restatement of
+tests/filter_cases.py (pinned to the reference's C_matchRef and C_matrixEE on the CPU, in tests/test_filter.py).  Every case
+compares every read: the stage code, the kept window, the two counts of the screen and the k-mer counts as integers, EE as
+bit-equal doubles, written files as bytes; the complexity value at relative 1e-12.  The same cases run under the emulator
+(tests/test_emu_filter.py)."""
+import pytest
+
+import filter_cases as fc
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def api():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    from dada2_amd import api as a
+    return a
+
+
+@pytest.mark.parametrize("name", fc.CASE_NAMES)
+def test_case_equals_the_restatement(api, name):
+    fc.CASES[name](api)
