@@ -6,10 +6,11 @@
 // word_size letters, its `len` windows) for the reference and for its reverse complement (R/filter.R:1183) as ONE sorted array of
 // distinct keys with two flag bits, in the key form of filter.inc.hip, and the two tables pow(10.0, -q / 10.0) per quality
 // CHARACTER (offset 33 and 64) with the host's pow, so that every term of the EE sum is the reference's bit for bit.
-// dada2hip_filter_reads cuts the call into pieces of at most FT_PIECE_READS reads / FT_PIECE_BYTES bytes and runs them through two
-// slots, each with pinned staging, device buffers and a stream of its own: while the kernels of one piece run, the host copies the
-// next piece into the other slot's pinned buffers and queues its upload, so the copy of piece k + 1 runs under the kernels of
-// piece k.  The Shannon number of seqComplexity (:1271-1275) is computed here from the device's integer counts.
+// dada2hip_filter_reads cuts the call into pieces of at most FT_PIECE_READS reads / FT_PIECE_BYTES bytes (DADA2HIP_FILTER_PIECE,
+// DADA2HIP_FILTER_PIECE_BYTES: fewer, for the tests) and runs them through two slots, each with pinned staging, device buffers and
+// a stream of its own: while the kernels of one piece run, the host copies the next piece into the other slot's pinned buffers and
+// queues its upload, so the copy of piece k + 1 runs under the kernels of piece k.  The Shannon number of seqComplexity
+// (:1271-1275) is computed here from the device's integer counts.
 #pragma once
 
 namespace {
@@ -221,10 +222,12 @@ void filter_reads_body(dada2hip_filter *m, int64_t n, const char *seq, const cha
   };
   struct Drain { dada2hip_filter *m; ~Drain() { for (FtSlot &S : m->slot) if (S.busy) { (void)hipStreamSynchronize(S.st); S.busy = false; } } } drain{m};
 
+  const int64_t piece_reads = knobs().filter_piece > 0 ? std::min<int64_t>(knobs().filter_piece, FT_PIECE_READS) : FT_PIECE_READS;
+  const int64_t piece_bytes = knobs().filter_piece_bytes > 0 ? std::min<int64_t>(knobs().filter_piece_bytes, FT_PIECE_BYTES) : FT_PIECE_BYTES;
   int64_t r0 = 0;
   for (int piece = 0; r0 < n; piece++) {
     int64_t r1 = r0 + 1;
-    while (r1 < n && r1 - r0 < FT_PIECE_READS && offsets[r1 + 1] - offsets[r0] <= FT_PIECE_BYTES) r1++;
+    while (r1 < n && r1 - r0 < piece_reads && offsets[r1 + 1] - offsets[r0] <= piece_bytes) r1++;
     FtSlot &S = m->slot[piece & 1];
     harvest(S);
     auto t_up = clk::now();

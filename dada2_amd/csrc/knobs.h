@@ -6,6 +6,7 @@
 // and none changes a result - they choose engines, kernel families and buffer sizes, which the parity tests sweep.
 // The variables read are exactly the ones named beside the fields of Knobs below (DESIGN.md has the same list as a table).
 #pragma once
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -68,6 +69,9 @@ struct Knobs {
   int collapse_scan = 1;              // DADA2HIP_COLLAPSE_SCAN=0       ... every screened pair is aligned (the diagonal bound is not used)
   int collapse_join = 1;              // DADA2HIP_COLLAPSE_JOIN=0       ... every (query, ref) pair is scanned (no prefix-key join)
   int tax_slab = 256;                 // DADA2HIP_TAX_SLAB=n            assignTaxonomy: queries of at most n k-mers are summed out of an LDS slab (0 = every query gathers from the table; at most 512)
+  long long tax_chunk = 0;            // DADA2HIP_TAX_CHUNK=n           ... queries per chunk of a pass (at least 1; at most, and unset, what keeps the per-tile records within 64 MB)
+  long long filter_piece = 0;         // DADA2HIP_FILTER_PIECE=n        filterAndTrim: reads per piece of a call (at least 1; at most, and unset, 65 536)
+  long long filter_piece_bytes = 0;   // DADA2HIP_FILTER_PIECE_BYTES=n  ... bases per piece (at least 1; at most, and unset, 32 MiB; a longer read is a piece of its own)
   int species_cand = 1 << 20;         // DADA2HIP_SPECIES_CAND=n        assignSpecies: records of the candidate buffer and of the hit buffer (a launch that counts more is re-run in pieces)
   int species_chunk = 8192;           // DADA2HIP_SPECIES_CHUNK=n       ... distinct queries per pass over the references (at most 8 192: the presence bitmap is sized for it)
   bool derep_zlib = false;           // DADA2HIP_DEREP_INFLATE=zlib    .gz files through zlib's streaming inflate even where libdeflate is installed
@@ -126,6 +130,8 @@ struct Knobs {
     k.collapse_batch = I("DADA2HIP_COLLAPSE_BATCH", 0); k.collapse_scan = I("DADA2HIP_COLLAPSE_SCAN", 1);
     k.collapse_join = I("DADA2HIP_COLLAPSE_JOIN", 1);
     k.tax_slab = I("DADA2HIP_TAX_SLAB", 256);
+    auto P = [&](const char *n) -> long long { const char *e = S(n); return e ? std::max(1ll, std::atoll(e)) : 0ll; };   // a size: 0 = unset
+    k.tax_chunk = P("DADA2HIP_TAX_CHUNK"); k.filter_piece = P("DADA2HIP_FILTER_PIECE"); k.filter_piece_bytes = P("DADA2HIP_FILTER_PIECE_BYTES");
     k.species_cand = I("DADA2HIP_SPECIES_CAND", 1 << 20); k.species_chunk = I("DADA2HIP_SPECIES_CHUNK", 8192);
     if (const char *e = S("DADA2HIP_DEREP_INFLATE")) k.derep_zlib = !std::strcmp(e, "zlib");
     if (const char *e = S("DADA2HIP_DEREP_TIMES")) k.derep_times = !std::strcmp(e, "1");

@@ -154,7 +154,8 @@ double taxonomy_run(const dada2hip_taxonomy *m, const std::vector<TaxQuery> &Q, 
   best.resize(list.size() * npass); ntie.resize(list.size() * npass); winner.resize(list.size() * npass);
   if (list.empty()) return 0.0;
   const size_t per_query = (size_t)npass * ntiles * sizeof(TaxPart);
-  const size_t chunk = std::max<size_t>(1, std::min<size_t>(((size_t)64 << 20) / per_query, (size_t)INT32_MAX / 2 / ntiles));
+  const size_t chunk_max = std::max<size_t>(1, std::min<size_t>(((size_t)64 << 20) / per_query, (size_t)INT32_MAX / 2 / ntiles));
+  const size_t chunk = knobs().tax_chunk > 0 ? std::min<size_t>((size_t)knobs().tax_chunk, chunk_max) : chunk_max;   // DADA2HIP_TAX_CHUNK
   DevBuf<int32_t> d_koff, d_qid, d_ntie, d_winner;
   DevBuf<uint16_t> d_karr, d_bpos;
   DevBuf<long long> d_boff;

@@ -51,9 +51,13 @@
  *   DADA2HIP_COLLAPSE_JOIN=0           ... every (query, ref) pair is scanned (no prefix-key join)
  *   DADA2HIP_TAX_SLAB=<n>              dada2hip_taxonomy_assign: queries of at most n valid k-mers are summed out of an LDS slab, longer
  *                                      ones gather from the table (default 256, at most 512; 0 = every query gathers)
+ *   DADA2HIP_TAX_CHUNK=<n>             ... queries per chunk of a pass (at least 1; default and at most what keeps the per-tile records
+ *                                      within 64 MB)
  *   DADA2HIP_SPECIES_CAND=<n>          dada2hip_species_match: records of the candidate and hit buffers (default 1 048 576; a launch
  *                                      that counts more is run again in pieces)
  *   DADA2HIP_SPECIES_CHUNK=<n>         ... distinct queries per pass over the references (default and at most 8 192)
+ *   DADA2HIP_FILTER_PIECE=<n>          dada2hip_filter_reads: reads per piece of a call (at least 1; default and at most 65 536)
+ *   DADA2HIP_FILTER_PIECE_BYTES=<n>    ... bases per piece (at least 1; default and at most 32 MiB; a longer read is a piece of its own)
  *   DADA2HIP_PROFILE=1, DADA2HIP_V2_SUMMARY, DADA2HIP_V2_DEBUG   per-launch device times in the stats; traces on stderr
  * Test / tuning knobs (sizes of rings and grids, forced growth paths, injected failures) are listed with their meaning in
  * knobs.h and DESIGN.md §10b; they are not part of the interface.

@@ -335,6 +335,34 @@ def check_pairs(api, idx):
     return len(idx)
 
 
+STRIDED_PAIRS = 2 * 16384 + 1                # k_collapse_scan's grid is capped at 16 384 blocks: every block a second pair, block 0 a third
+
+
+def strided_pairs():
+    """The fixture's pairs of its most frequent min_overlap, repeated to 32 769 and turned by one: (indices into the fixture,
+    min_overlap).  Pair i and pair i + 16 384, which one block takes one after the other, are different pairs."""
+    g = golden()
+    vals, cnt = np.unique(g["min_overlap"], return_counts=True)
+    mo = int(vals[np.argmax(cnt)])
+    sel = np.flatnonzero(g["min_overlap"] == mo)
+    idx = np.roll(np.resize(sel, STRIDED_PAIRS), 1)
+    assert (idx[16384:] != idx[:-16384]).all() and (idx[1:] != idx[:-1]).all()
+    return idx, mo
+
+
+def check_strided_pairs(api):
+    """One dada2hip_collapse_pairs call of 32 769 pairs against the fixture's brute-force scan, as check_pairs."""
+    g = golden()
+    idx, mo = strided_pairs()
+    got = api.collapse_pairs([str(x) for x in g["queries"][idx]], [str(x) for x in g["refs"][idx]], min_overlap=mo)
+    want = g["scan"][idx]
+    assert len({tuple(r) for r in want[:, [0, 3]].tolist()}) >= 4          # screened out, rejected by the bound, to the aligner; both screen bits
+    bad = np.flatnonzero((got != want).any(axis=1))
+    assert bad.size == 0, (mo, "first at pair", int(bad[0]), "of", int(bad.size), str(g["queries"][idx[bad[0]]]), str(g["refs"][idx[bad[0]]]),
+                           got[bad[0]].tolist(), want[bad[0]].tolist())
+    return len(idx)
+
+
 def emu_run():
     """The emulator's job (tests/test_emu_collapse.py): collapse_pairs on 300 fixture pairs, the whole function on a 60-column
     cut of the generated table in batches of 8 against the restatement, nweval on 50 pairs."""

@@ -9,6 +9,8 @@ Python strings, line by line against R/filter.R:
   matrix_ee         C_matrixEE (:35-49): ee += pow(10.0, -q / 10.0) in order (math.pow is libm's pow)
   kmer_counts, complexity   oligonucleotideFrequency's bins and sindex (:1271-1275)
   restate_fastq, restate_paired   the file level: chunks only matter through the Auto quality offset (the first chunk's)
+The pieces a call is cut into (DADA2HIP_FILTER_PIECE, DADA2HIP_FILTER_PIECE_BYTES) change no result: case_pieces runs one batch under
+small pieces and counts them; strided_batch is the batch past one piece, 8 192 waves and 16 384 blocks (tests/test_gpu_filter.py).
 Every comparison with the library is exact (integers, byte strings, bit-equal doubles) except the complexity value, relative 1e-12:
 sixteen fp64 terms summed by R in long double, a few ulp at most."""
 import gzip
@@ -298,6 +300,20 @@ def check_reads(api, ctx, seqs, quals, what="", kmers=False, **kw):
             gc = float(got["complexity"][i])
             assert (math.isnan(c) and math.isnan(gc)) or abs(gc - c) <= 1e-12 * abs(c), (what, i, gc, c)
     return [w["code"] for w in want]
+
+
+def with_env(env, f):
+    env = {k: str(v) for k, v in (env or {}).items()}
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        return f()
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
 
 
 def open_ctx(api, word_size=16, screen=True):
@@ -720,6 +736,239 @@ def case_vignette(api, tmp, denoise=True):
         assert len(m) > 0 and sum(r["abundance"] for r in m) <= counts[1]
 
 
+# ---- the pieces of a call ---------------------------------------------------------------------------------------------------------
+
+PIECE_READS, PIECE_BYTES = 1 << 16, 32 << 20                               # the library's own limits, and what it uses unset
+
+
+def cut_pieces(lens, reads=None, nbytes=None):
+    """[(first read, one past the last)] of the pieces dada2hip_filter_reads cuts reads of these lengths into: a piece takes reads
+    while it has fewer than `reads` and the next one still ends within `nbytes` of its start; its first read always."""
+    reads = min(max(reads, 1), PIECE_READS) if reads is not None else PIECE_READS
+    nbytes = min(max(nbytes, 1), PIECE_BYTES) if nbytes is not None else PIECE_BYTES
+    out, r0, n = [], 0, len(lens)
+    while r0 < n:
+        r1, b = r0 + 1, lens[r0]
+        while r1 < n and r1 - r0 < reads and b + lens[r1] <= nbytes:
+            b += lens[r1]
+            r1 += 1
+        out.append((r0, r1))
+        r0 = r1
+    return out
+
+
+def pieces_of(st, nbytes):
+    """The pieces behind a call's stats: upload_bytes is 2 x bytes + (reads + pieces) x 8."""
+    rest = st["upload_bytes"] - 2 * nbytes - 8 * st["reads_in"]
+    assert rest >= 0 and rest % 8 == 0, (st, nbytes)
+    return rest // 8
+
+
+COUNTED = ("reads_in", "reads_kept") + tuple("dropped_" + s for s in STAGES[1:])
+
+
+def same_outputs(got, base, what):
+    assert sorted(got) == sorted(base), what
+    for k in base:
+        a, b = got[k], base[k]
+        if a.dtype == np.float64:                                          # bit for bit (NaN included)
+            a, b = a.view(np.uint64), b.view(np.uint64)
+        bad = np.flatnonzero((a != b).reshape(len(a), -1).any(axis=1))
+        assert bad.size == 0, (what, k, "first at read", int(bad[0]), got[k][bad[0]].tolist(), base[k][bad[0]].tolist())
+
+
+def pieces_reads():
+    """300 reads, the lengths 0, 1, 64 and 65 among them, one of 1 500 nt at index 137."""
+    rng = random.Random(113)
+    seqs, quals = mixed_reads(rng, 299, lengths=(0, 1, 16, 30, 47, 64, 65, 100, 150, 251), p_phix=0.3, p_n=0.5)
+    ls, lq = mixed_reads(rng, 1, lengths=(1500,), p_phix=1.0)
+    seqs[137:137] = ls
+    quals[137:137] = lq
+    return seqs, quals
+
+
+def case_pieces(api, tmp):
+    """One batch under small pieces: every output and every count is the default run's and the restatement's, and the pieces
+    happened - the second piece, a slot used a second time, the stats summed over pieces, the cut by bytes; then the file level with
+    four pieces per chunk."""
+    seqs, quals = pieces_reads()
+    lens = [len(s) for s in seqs]
+    n, nbytes = len(seqs), sum(lens)
+    assert n == 300 and {0, 1, 64, 65} <= set(lens) and lens.count(1500) == 1 and lens[137] == 1500
+    kw = dict(rm_phix=True, max_ee=0.05, trunc_len=40, max_n=1, kmers=True)
+    # (setting, the cut it stands for, the least number of pieces): 299 reads leave a second piece of one read, 1 499 bytes give
+    # the long read a piece of its own
+    settings = [({}, {}, 1)] + [({"DADA2HIP_FILTER_PIECE": r}, {"reads": r}, 2 if r == 299 else 3) for r in (1, 2, 7, 64, 299)]
+    settings += [({"DADA2HIP_FILTER_PIECE_BYTES": b}, {"nbytes": b}, 3) for b in (400, 1499)]
+    settings += [({"DADA2HIP_FILTER_PIECE": 10**9, "DADA2HIP_FILTER_PIECE_BYTES": 10**12}, {}, 1),      # past the limits: the limits
+                 ({"DADA2HIP_FILTER_PIECE": 0, "DADA2HIP_FILTER_PIECE_BYTES": -5}, {"reads": 1, "nbytes": 1}, 3)]   # below 1: 1
+    assert (137, 138) in cut_pieces(lens, nbytes=1499) and len(cut_pieces(lens, nbytes=400)) > n // 10
+    assert all(b - a <= 12 for a, b in cut_pieces(lens, nbytes=400))       # "every few reads"
+    with open_ctx(api) as ctx:
+        base = None
+        for env, cut, least in settings:
+            st = {}
+            got = with_env(env, lambda: api.filter_reads(seqs, quals, ctx, stats=st, **kw))
+            codes = with_env(env, lambda: check_reads(api, ctx, seqs, quals, "pieces %r" % (env,), **kw))
+            if base is None:
+                base, base_st = got, st
+                assert all(codes.count(c) >= 10 for c in (0, 5, 7, 9, 10)), [codes.count(c) for c in range(12)]
+            same_outputs(got, base, env)
+            assert got["code"].tolist() == codes, env
+            for k in COUNTED:
+                assert st[k] == base_st[k], (env, k, st[k], base_st[k])
+            assert st["reads_in"] == n and st["reads_kept"] == codes.count(0), (env, st)
+            for c in range(1, 12):
+                assert st["dropped_" + STAGES[c]] == codes.count(c), (env, STAGES[c], st)
+            want = len(cut_pieces(lens, **cut))
+            assert pieces_of(st, nbytes) == want >= least, (env, pieces_of(st, nbytes), want, least)
+        assert len(cut_pieces(lens, reads=7)) == 43 and len(cut_pieces(lens, reads=299)) == 2 and len(cut_pieces(lens)) == 1
+        # ---- the file level: chunks of 100 reads in pieces of 30 -> 4 + 4 + 2 pieces (and twice that for a pair of files) ----
+        rf, rr = paired_records(250, seed=114)
+        inf, inr = os.path.join(tmp, "pc_F.fastq"), os.path.join(tmp, "pc_R.fastq")
+        write_fastq(inf, rf)
+        write_fastq(inr, rr)
+        fkw = dict(trunc_len=60, max_ee=2)
+        kept, counts = restate_fastq(rf, params(rm_phix=True, **fkw), phix())
+        kf, kr, pcounts = restate_paired(rf, rr, params(rm_phix=True, **fkw), phix())
+        assert 0 < counts[1] < counts[0] and 0 < pcounts[1] < counts[1]
+        bf, br = sum(len(r[1]) for r in rf), sum(len(r[1]) for r in rr)
+        outs = {}
+        for env, npieces in (({}, 3), ({"DADA2HIP_FILTER_PIECE": 30}, 10)):
+            out = os.path.join(tmp, "pc_out.fastq")
+            st = {}
+            got = with_env(env, lambda: api.fastq_filter(inf, out, compress=False, n=100, rm_phix=True, ctx=ctx, stats=st, **fkw))
+            assert got == counts and st["reads_in"] == counts[0] and st["reads_kept"] == counts[1], (env, got, counts, st)
+            assert read_text(out) == fastq_text(kept), env
+            assert pieces_of(st, bf) == npieces, (env, pieces_of(st, bf))
+            of, orv = os.path.join(tmp, "pc_oF.fastq.gz"), os.path.join(tmp, "pc_oR.fastq.gz")
+            pst = {}
+            got = with_env(env, lambda: api.fastq_paired_filter((inf, inr), (of, orv), n=100, rm_phix=True, ctx=ctx, stats=pst, **fkw))
+            assert got == pcounts and pst["reads_in"] == pcounts[0] and pst["reads_kept"] == pcounts[1], (env, got, pcounts, pst)
+            assert read_text(of) == fastq_text(kf) and read_text(orv) == fastq_text(kr), env
+            rest = pst["upload_bytes"] - 2 * (bf + br) - 8 * 2 * len(rf)   # (the bytes are both files', reads_in the forward file's)
+            assert rest == 8 * 2 * npieces, (env, rest)
+            outs[bool(env)] = ({k: st[k] for k in COUNTED}, {k: pst[k] for k in COUNTED})
+        assert outs[True] == outs[False]
+
+
+# ---- past one piece, 8 192 waves and 16 384 blocks -----------------------------------------------------------------------------------
+
+STRIDED_N, STRIDED_POOL = 2 * PIECE_READS + 1, 4096                        # three pieces; every wave of k_filter_scan takes 8 reads of a piece
+STRIDED_LENGTHS = (0, 1, 15, 16, 17, 20, 30, 47, 64, 65, 100, 129, 150)
+STRIDED_KW = dict(rm_phix=True, max_ee=0.05, trunc_len=40, max_n=1, kmer_size=2)
+_STRIDED = {}
+
+
+def strided_pool(which="phix"):
+    """4 096 distinct reads and their restatement as arrays, once per process: ("phix") against the genome, whose word table the
+    kernel keeps in LDS, or ("global") against the 9 000-nt random reference of case_screen_in_global_memory, every seventh read
+    long enough replaced by a cut of it."""
+    if which not in _STRIDED:
+        rng = random.Random(115)
+        seqs, quals = mixed_reads(rng, STRIDED_POOL - 2, lengths=STRIDED_LENGTHS, p_phix=0.25, p_n=0.3)
+        ls, lq = mixed_reads(rng, 2, lengths=(1500,), p_phix=1.0)
+        seqs[1000:1000] = ls[:1]
+        quals[1000:1000] = lq[:1]
+        seqs[3000:3000] = ls[1:]
+        quals[3000:3000] = lq[1:]
+        ref = phix()
+        if which == "global":
+            ref = rand_seq(random.Random(109), 9000)                       # case_screen_in_global_memory's
+            r2 = random.Random(116)
+            for i in range(3, len(seqs), 7):
+                if len(seqs[i]) >= 47:
+                    at = r2.randrange(9000 - len(seqs[i]))
+                    cut = ref[at: at + len(seqs[i])]
+                    seqs[i] = rc(cut) if r2.random() < 0.5 else cut
+        # (distinct but for the few reads a length of 0 or 1 allows)
+        assert len(seqs) == STRIDED_POOL and len(set(zip(seqs, quals))) >= STRIDED_POOL - 2 * (STRIDED_POOL // len(STRIDED_LENGTHS) + 1)
+        assert auto_offset(quals) == 33
+        P = params(**STRIDED_KW)
+        want = [restate_read(s, q, P, ref, 33) for s, q in zip(seqs, quals)]
+        kept = [s[w["off"]: w["off"] + w["len"]] for s, w in zip(seqs, want)]
+        arr = {"code": np.array([w["code"] for w in want], dtype=np.int32),
+               "window": np.array([(w["off"], w["len"]) for w in want], dtype=np.int32),
+               "ee": np.array([w["ee"] for w in want], dtype=np.float64),
+               "hits": np.array([w["hits"] for w in want], dtype=np.int32),
+               "kmer_counts": np.array([kmer_counts(k, 2) for k in kept], dtype=np.int32),
+               "complexity": np.array([complexity(k, 2) for k in kept], dtype=np.float64)}
+        counts = np.bincount(arr["code"], minlength=12)
+        assert all(counts[c] >= 20 for c in (0, 5, 7, 9, 10)), (which, counts.tolist())
+        _STRIDED[which] = dict(seqs=seqs, quals=quals, ref=ref, want=arr)
+    return _STRIDED[which]
+
+
+def strided_order():
+    """pool[(i * 2654435761 + i // 4096) % 4096]: neighbours differ, and so do reads 8 192 (a wave's next read), 16 384 (a block's)
+    or a piece apart - the product alone has period 4 096, which divides all three, so every run of 4 096 is turned by one more."""
+    i = np.arange(STRIDED_N, dtype=np.uint64)
+    idx = ((i * np.uint64(2654435761) + i // np.uint64(STRIDED_POOL)) % np.uint64(STRIDED_POOL)).astype(np.int64)
+    for d in (1, 4096, 8192, 16384, PIECE_READS, 2 * PIECE_READS):
+        assert (idx[d:] != idx[:-d]).all(), d
+    return idx
+
+
+def check_strided_batch(api, which):
+    """One dada2hip_filter_reads call on 131 073 reads against the tiled restatement of the pool, every output of every read."""
+    d = strided_pool(which)
+    idx = strided_order()
+    seqs, quals = [d["seqs"][i] for i in idx], [d["quals"][i] for i in idx]
+    nbytes = sum(len(s) for s in seqs)
+    st = {}
+    with api.FilterContext(d["ref"], 16) as ctx:
+        assert ctx.stats["table_in_lds"] == (1 if which == "phix" else 0), ctx.stats
+        got = api.filter_reads(seqs, quals, ctx, kmers=True, stats=st, **STRIDED_KW)
+    want = {k: v[idx] for k, v in d["want"].items()}
+    for k in ("code", "window", "hits", "kmer_counts"):
+        bad = np.flatnonzero((got[k] != want[k]).reshape(STRIDED_N, -1).any(axis=1))
+        assert bad.size == 0, (which, k, "first at read", int(bad[0]), "of", int(bad.size), got[k][bad[0]].tolist(), want[k][bad[0]].tolist())
+    bad = np.flatnonzero(got["ee"].view(np.uint64) != want["ee"].view(np.uint64))
+    assert bad.size == 0, (which, "ee", "first at read", int(bad[0]), "of", int(bad.size), got["ee"][bad[0]].hex(), want["ee"][bad[0]].hex())
+    g, w = got["complexity"], want["complexity"]
+    with np.errstate(invalid="ignore"):
+        ok = (np.isnan(g) & np.isnan(w)) | (np.abs(g - w) <= 1e-12 * np.abs(w))
+    bad = np.flatnonzero(~ok)
+    assert bad.size == 0, (which, "complexity", "first at read", int(bad[0]), "of", int(bad.size), float(g[bad[0]]), float(w[bad[0]]))
+    counts = np.bincount(want["code"], minlength=12)
+    assert st["reads_in"] == STRIDED_N and st["reads_kept"] == counts[0], (st, counts.tolist())
+    for c in range(1, 12):
+        assert st["dropped_" + STAGES[c]] == counts[c], (STAGES[c], st, counts.tolist())
+    assert pieces_of(st, nbytes) == 3 == len(cut_pieces([len(s) for s in seqs])), st
+    return st
+
+
+def check_strided_file(api, tmp):
+    """The same batch as a FASTQ file through dada2hip_filter_fastq with its default chunk, plain in and plain out."""
+    d = strided_pool("phix")
+    idx = strided_order()
+    w = d["want"]
+    rec = ["%s\n+\n%s\n" % (s, q) for s, q in zip(d["seqs"], d["quals"])]
+    kept = ["%s\n+\n%s\n" % (s[o: o + n], q[o: o + n]) for s, q, (o, n) in zip(d["seqs"], d["quals"], w["window"].tolist())]
+    src, out = os.path.join(tmp, "strided.fastq"), os.path.join(tmp, "strided_out.fastq")
+    with open(src, "w") as fh:
+        fh.write("".join("@r%d\n%s" % (i, rec[p]) for i, p in enumerate(idx.tolist())))
+    code = w["code"][idx]
+    want_text = "".join("@r%d\n%s" % (i, kept[p]) for i, p in enumerate(idx.tolist()) if code[i] == 0)
+    counts = np.bincount(code, minlength=12)
+    st = {}
+    kw = {k: v for k, v in STRIDED_KW.items() if k not in ("rm_phix", "kmer_size")}
+    with api.FilterContext(d["ref"], 16) as ctx:
+        got = api.fastq_filter(src, out, compress=False, rm_phix=True, ctx=ctx, stats=st, **kw)
+    assert got == (STRIDED_N, int(counts[0])) and 0 < counts[0] < STRIDED_N, (got, counts.tolist())
+    with open(out) as fh:
+        text = fh.read()
+    if text != want_text:
+        a, b = text.split("\n"), want_text.split("\n")
+        at = next((i for i, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
+        raise AssertionError(("the written file differs", "first at line", at, a[at: at + 1], b[at: at + 1], len(a), len(b)))
+    assert st["reads_in"] == STRIDED_N and st["reads_kept"] == counts[0], (st, counts.tolist())
+    for c in range(1, 12):
+        assert st["dropped_" + STAGES[c]] == counts[c], (STAGES[c], st, counts.tolist())
+    assert pieces_of(st, sum(len(d["seqs"][p]) for p in idx.tolist())) == 3, st
+    return st
+
+
 def _raises(exc, fn, text=None, code=None):
     try:
         fn()
@@ -766,7 +1015,7 @@ def _with_tmp(fn, **kw):
 CASES = {"lengths": case_lengths, "batches": case_batches, "letters": case_letters, "truncq": case_truncq, "trims": case_trims,
          "minq": case_minq, "ee_threshold": case_ee_threshold, "screen": case_screen,
          "screen_in_global_memory": case_screen_in_global_memory, "complexity": case_complexity, "paired": _with_tmp(case_paired),
-         "files": _with_tmp(case_files), "fixtures": _with_tmp(case_fixtures), "vignette": _with_tmp(case_vignette),
+         "files": _with_tmp(case_files), "pieces": _with_tmp(case_pieces), "fixtures": _with_tmp(case_fixtures), "vignette": _with_tmp(case_vignette),
          "input_errors": _with_tmp(case_input_errors)}
 CASE_NAMES = tuple(CASES)
 

@@ -366,6 +366,63 @@ def _open_empty(api):
     _lib.check(_lib.lib().dada2hip_species_open(0, (C.c_char_p * 1)(), 0, C.byref(h), None, eb, 512), eb)
 
 
+# ---- past one sweep of k_species_seed (8 192 references: 2 048 blocks of 4 waves), -m gpu only -----------------------------------------
+STRIDED_NREF = 8200
+_STRIDED = {}
+
+
+def strided_data():
+    """8 200 references of 40-90 nt, a few with an N and a few of 31, 32 and 33 nt; 21 queries: 35 nt cut from the references either
+    side of a wave's and a block's second turn (0, 1, 4 095, 4 096, 8 191, 8 192, 8 193, the last), one embedded in every third
+    reference, eight random ones, a whole reference of 31 nt, one across a reference's N and two reverse complements.  Built once per process, with its restatement."""
+    if not _STRIDED:
+        rng = random.Random(11)
+        refs = [_rand(rng, rng.randint(40, 90)) for _ in range(STRIDED_NREF)]
+        for i, n in ((5000, 31), (5001, 32), (5002, 33), (8194, 31), (8195, 32), (8196, 33), (17, 33)):
+            refs[i] = _rand(rng, n)
+        common = _rand(rng, 35)
+        for i in range(2, STRIDED_NREF, 3):                      # (2, 5, ...: 8 192 and 8 195 - too short - among them, 0 and 4 095 not)
+            if len(refs[i]) >= 35:
+                refs[i] = _embed(rng, common, len(refs[i]), rng.randint(0, len(refs[i]) - 35))
+        for i in (7, 4100, 8190, 8197, 8199):                    # an N away from the start, where the cuts below come from
+            refs[i] = refs[i][:38] + "N" + refs[i][39:]
+        refs[8198] = refs[8198][:10] + "N" + refs[8198][11:]     # ... and one inside what would be an occurrence
+        at = (0, 1, 4095, 4096, 8191, 8192, 8193, STRIDED_NREF - 1)
+        seqs = [refs[i][:35] if i % 2 else refs[i][len(refs[i]) - 35:] for i in at]
+        seqs += [common] + [_rand(rng, 35) for _ in range(8)] + [refs[8194]]
+        seqs += [refs[8198][:35].replace("N", "A"), rc(refs[4098][:35]), rc(refs[8188][3:38])]   # the N; found with try_rc only
+        assert len(seqs) == 21 and len(refs[8194]) == 31 and all("N" not in q for q in seqs)
+        want = {t: restate_hits(seqs, refs, t) for t in (False, True)}
+        for k, i in enumerate(at):
+            assert i in want[False][k], (k, i)
+        assert len(want[False][8]) > 2600 and 8192 in want[False][8] and 8194 in want[False][17] and want[True][18] == []
+        assert want[False][19] == want[False][20] == [] and want[True][19] == [4098] and want[True][20] == [8188]
+        _STRIDED.update(refs=refs, seqs=seqs, want=want)
+    return _STRIDED
+
+
+def check_strided(api):
+    """The hit lists against the restatement with try_rc off and on, by default and with a candidate buffer of 256 records, which
+    the embedded query alone overflows: the range is halved (r0 > 0) down to where a sweep fits."""
+    d = strided_data()
+    out = {}
+    with api.SpeciesModel((d["refs"], _ids(len(d["refs"])))) as m:
+        for t in (False, True):
+            for env in (None, {"DADA2HIP_SPECIES_CAND": 256}):
+                st = {}
+                got = device_hits(api, None, d["seqs"], try_rc=t, env=env, stats=st, model=m)
+                want = d["want"][t]
+                assert got == want, (t, env, [(j, got[j][:8], want[j][:8]) for j in range(len(want)) if got[j] != want[j]][:5])
+                out[(t, env is not None)] = st
+            a, b = out[(t, False)], out[(t, True)]
+            assert a["candidate_reruns"] == 0 and b["candidate_reruns"] >= 1, (a, b)
+            for k in ("candidates", "hits", "windows", "windows_past_bitmap"):
+                assert a[k] == b[k], (t, k, a, b)
+            assert a["hits"] == sum(len(w) for w in d["want"][t]) and a["candidates"] >= a["hits"] > 256, a
+            assert a["windows"] > 0 and a["references"] == STRIDED_NREF, a
+    return out
+
+
 CASES = {"placement": case_placement, "boundaries": case_boundaries, "nonacgt_plane": case_nonacgt_plane, "keys": case_keys,
          "multiplicity": case_multiplicity, "try_rc": case_try_rc, "overflow": case_overflow, "chunking": case_chunking,
          "sweep": case_sweep, "two_calls": case_two_calls, "example": case_example, "input_errors": case_input_errors}

@@ -328,13 +328,56 @@ def check_case(api, name, slab_settings=(None, 0)):
     return int(ran.sum()), int((want_ntie > 1).sum()), got, stats
 
 
+CHUNKED = ("ngenus129", "lengths", "try_rc")                     # three tiles; the slab and the gather instance in one call; tryRC's two passes
+TAX_CHUNKS = (1, 3)
+
+
+def expected_launches(st, try_rc, chunk=None):
+    """Two launches (sums, combine) per chunk of every pass over a non-empty list: tryRC's two passes over all classified queries,
+    then the gather and the slab instance over theirs."""
+    def chunks(n):
+        return 0 if n == 0 else (1 if chunk is None else -(-n // chunk))
+    return 2 * ((2 * chunks(st["classified"]) if try_rc else 0) + chunks(st["slab_queries"]) + chunks(st["gather_queries"]))
+
+
+def check_chunks(api, name, chunks=TAX_CHUNKS):
+    """check_case under DADA2HIP_TAX_CHUNK = 1, 3 and unset: the criteria hold under each, the outputs are identical, and the
+    chunks happened (the queries of a later chunk land at their own offset; the buffers are used again).  Returns the unset run's
+    check_case result."""
+    c = load_case(name)
+    base = check_case(api, name)
+    for st in base[3]:
+        assert st["launches"] == expected_launches(st, c["try_rc"]), (name, st)
+    for chunk in chunks:
+        e, t, got, stats = with_env({"DADA2HIP_TAX_CHUNK": chunk}, lambda: check_case(api, name))
+        for k in ("tax", "boot", "boot_tax", "ntie"):
+            assert np.array_equal(got[k], base[2][k]), (name, "chunks of", chunk, "differ in", k)
+        for st, st0 in zip(stats, base[3]):
+            assert {k: st[k] for k in TAXONOMY_COUNTS} == {k: st0[k] for k in TAXONOMY_COUNTS}, (name, chunk, st, st0)
+            assert st["launches"] == expected_launches(st, c["try_rc"], chunk) > st0["launches"], (name, chunk, st, st0)
+    # a value past the automatic one is the automatic one; one below 1 is 1
+    for val, chunk in ((10**9, None), (0, 1)):
+        st = {}
+        with device_model(api, name) as m:
+            got = with_env({"DADA2HIP_TAX_CHUNK": val},
+                           lambda: api.assign_taxonomy_raw(c["seqs"], m, try_rc=c["try_rc"], seed=c["seed"], unifs=c["unifs"], stats=st))
+        assert st["launches"] == expected_launches(st, c["try_rc"], chunk), (name, val, st)
+        for k in ("tax", "boot", "boot_tax", "ntie"):
+            assert np.array_equal(got[k], base[2][k]), (name, "DADA2HIP_TAX_CHUNK", val, k)
+    return base
+
+
+TAXONOMY_COUNTS = ("classified", "slab_queries", "gather_queries", "took_reverse_complement")
+
+
 def emu_run():
     """The emulator's job (tests/test_emu_taxonomy.py): the example data, a model of three tiles, the twins, the N query and
-    try_rc, each under the slab and the gather instance, held to check_case's criteria."""
+    try_rc, each under the slab and the gather instance, held to check_case's criteria; the cases of CHUNKED (the mixed lengths
+    among them) also in chunks of 1 and 3 queries (check_chunks)."""
     from dada2_amd import api
     entries = ties = 0
-    for name in ("example", "ngenus129", "twins", "len57", "broken_by_N", "try_rc"):
-        e, t, got, stats = check_case(api, name)
+    for name in ("example", "ngenus129", "twins", "lengths", "len57", "broken_by_N", "try_rc"):
+        e, t, got, stats = check_chunks(api, name) if name in CHUNKED else check_case(api, name)
         if name not in TIES_ARE_THE_POINT:
             entries += e
             ties += t

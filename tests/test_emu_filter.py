@@ -1,6 +1,10 @@
 """filterAndTrim under the emulator (tests/filter_cases.py, emu_run): the product's own host code - the word table of both
-strands, the expected-error tables, the pieces and the two slots of a call, the Shannon number, the FASTQ reader, the paired AND
-and the writer with its gzip members - and k_filter_scan, k_filter_ee and k_filter_kmers run on the CPU, in a subprocess with
+strands, the expected-error tables, the Shannon number, the FASTQ reader, the paired AND and the writer with its gzip members -
+and k_filter_scan, k_filter_ee and k_filter_kmers run on the CPU.  The pieces and the two slots of a call run in the case
+"pieces" alone (DADA2HIP_FILTER_PIECE from 1 to 299 reads and DADA2HIP_FILTER_PIECE_BYTES on 300 reads, 30 reads on files in
+chunks of 100: the second piece, a slot used again, the stats summed over pieces, the cut by bytes, each counted from
+upload_bytes); every other case is one piece in slot 0, and no case here makes a wave of k_filter_scan or a block of
+k_filter_kmers take a second read (that is tests/test_gpu_filter.py's batch of 131 073).  All of it in a subprocess with
 dada2_amd._lib pointed at the emulated library as in tests/test_emu_species.py, and are held to the cases of the GPU tests."""
 import os
 import subprocess

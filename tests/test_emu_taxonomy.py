@@ -2,7 +2,8 @@
 host's logf, the k-mer arrays, the uniform layout, the bootstrap counts - and k_tax_sums (slab and gather instance) and
 k_tax_combine run on the CPU, in a subprocess with dada2_amd._lib pointed at the emulated library as in
 tests/test_emu_collapse.py, and are held to the criteria of the GPU tests: the model table bit-equal to the restatement's, ntie
-exact, every pick in its tie set, boot recounted, the two instances / two calls identical, another seed only at ties."""
+exact, every pick in its tie set, boot recounted, the two instances / two calls identical, another seed only at ties; three
+cases also with the queries in chunks of 1 and 3 (DADA2HIP_TAX_CHUNK): identical outputs, the chunks counted from the launches."""
 import os
 import subprocess
 import sys

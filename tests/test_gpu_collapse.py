@@ -47,6 +47,11 @@ def test_collapse_pairs_match_the_fixture(api):
     assert cc.check_pairs(api, np.arange(6000)) == 6000
 
 
+def test_collapse_pairs_past_the_block_cap_of_the_scan(api):
+    """32 769 pairs in one call: every block of k_collapse_scan stages a second pair over its first, block 0 a third."""
+    assert cc.check_strided_pairs(api) == 32769
+
+
 def test_collapse_pairs_with_lengths_either_side_of_the_word_boundaries(api):
     """1, 2, 31, 32, 33, 63, 64, 65, 250, 251, 256, 257 and 600 nt, each against each; a copy, a shifted copy, a contained piece, a
     one-mismatch copy; minOverlap 1 to 700 (above 32: longer than the join's key; 700: above every length) - against brute force."""

@@ -36,6 +36,12 @@ def test_case_meets_the_criteria(api, name):
         assert tc.restated_flips(name) == [1, 3, 5, 7] and stats[0]["took_reverse_complement"] == 4, stats[0]
 
 
+@pytest.mark.parametrize("name", tc.CHUNKED)
+def test_chunks_of_queries_change_nothing(api, name):
+    """DADA2HIP_TAX_CHUNK = 1, 3 and unset: the criteria under each, identical outputs, two launches per extra chunk and instance."""
+    tc.check_chunks(api, name)
+
+
 def test_untied_picks_are_the_reference_runs(api):
     """Where the maximum is untied the device's pick is the reference's recorded pick, in both recorded runs."""
     c = tc.load_case("example")
