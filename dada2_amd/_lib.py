@@ -124,6 +124,7 @@ EXPORTS = [
     "dada2hip_species_open", "dada2hip_species_free", "dada2hip_species_match", "dada2hip_species_hits_offsets",
     "dada2hip_species_hits_refs", "dada2hip_species_hits_free",
     "dada2hip_filter_open", "dada2hip_filter_free", "dada2hip_filter_reads", "dada2hip_filter_fastq", "dada2hip_filter_fastq_paired",
+    "dada2hip_primers_reads", "dada2hip_primers_fastq",
 ]
 
 COLLAPSE_NSTATS = 16   # DADA2HIP_COLLAPSE_NSTATS
@@ -158,6 +159,20 @@ class CFilterParams(C.Structure):
                 ("max_ee", C.c_double), ("rm_lowcomplex", C.c_double),
                 ("rm_phix", C.c_int32), ("min_matches", C.c_int32), ("non_overlapping", C.c_int32), ("kmer_size", C.c_int32),
                 ("qual_offset", C.c_int32), ("reserved", C.c_int32)]
+
+
+PRIMERS_NSTATS = 24   # DADA2HIP_PRIMERS_NSTATS
+# the int64 words of the stats of dada2hip_primers_reads / _fastq, in order
+PRIMER_CODES = ("kept", "no_fwd", "no_rev", "nothing_left", "bad_letter")   # a read's code indexes this
+PRIMERS_STATS = ("reads_in", "reads_kept") + tuple("dropped_" + s for s in PRIMER_CODES[1:]) + (
+    "flipped", "multiple_matches", "hits_fwd", "hits_rev", "pieces", "tiles", "upload_bytes", "upload_us", "kernel_device_us",
+    "download_us", "parse_us", "deflate_us", "write_us", "total_us", "open_inflate_us")
+
+
+class CPrimerParams(C.Structure):
+    """dada2hip_primer_params"""
+    _fields_ = [("primer_fwd", C.c_char_p), ("primer_rev", C.c_char_p), ("max_mismatch", C.c_int32), ("trim_fwd", C.c_int32),
+                ("trim_rev", C.c_int32), ("orient", C.c_int32), ("allow_indels", C.c_int32), ("reserved", C.c_int32)]
 
 
 class CSampleInput(C.Structure):
@@ -321,6 +336,9 @@ def lib():
                                         vp, cp, C.c_size_t]
     L.dada2hip_filter_fastq_paired.argtypes = [vp, cp, cp, cp, cp, C.POINTER(CFilterParams), C.POINTER(CFilterParams), ip, C.c_int64,
                                                C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp, cp, C.c_size_t]
+    L.dada2hip_primers_reads.argtypes = [C.c_int64, vp, vp, C.POINTER(CPrimerParams), ip, vp, vp, vp, vp, vp, vp, vp, cp, C.c_size_t]
+    L.dada2hip_primers_fastq.argtypes = [cp, cp, C.POINTER(CPrimerParams), ip, C.c_int64, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                         vp, cp, C.c_size_t]
     L.dada2hip_trim_cache.argtypes = []
     L.dada2hip_trim_cache.restype = None
     _lib = L

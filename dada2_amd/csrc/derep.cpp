@@ -629,7 +629,7 @@ void bytes_append(Bytes &b, const char *p, size_t n) {
   const size_t at = b.size();
   if (b.capacity() < at + n) b.reserve(std::max(at + n, b.capacity() * 2));
   b.resize(at + n);
-  memcpy(b.data() + at, p, n);
+  if (n) memcpy(b.data() + at, p, n);                          // (an empty read into an empty blob: no memcpy on a null pointer)
 }
 
 // up to `limit` records into c; false on a malformed record or a damaged stream (err)
@@ -668,14 +668,23 @@ int fq_auto_offset(const FqChunk &c) {
   return m < 59 ? 33 : 64;
 }
 
+// Biostrings' complement of an IUPAC letter (A<->T C<->G M<->K R<->Y V<->B H<->D; W S N and anything else themselves)
+inline char fq_complement(char c) {
+  static const char from[] = "ACGTMKRYVBHD", to[] = "TGCAKMYRBVDH";
+  const char *p = c ? strchr(from, c) : nullptr;
+  return p ? to[p - from] : c;
+}
+
 struct FqWriter {
   std::string path;
   FILE *fp = nullptr;
   bool compress = false;
   int64_t us_deflate = 0, us_write = 0;
   ~FqWriter() { if (fp) fclose(fp); }
-  // the records of c with keep[i] != 0, cut to win[2 i], win[2 i + 1]
-  bool put(const FqChunk &c, const std::vector<uint8_t> &keep, const std::vector<int32_t> &win, std::string &err) {
+  // the records of c with keep[i] != 0, cut to win[2 i], win[2 i + 1]; where flip[i] != 0 (flip may be empty) the window is one of
+  // the read's reverse complement: its letters complemented and its qualities, both from the read's end backwards
+  bool put(const FqChunk &c, const std::vector<uint8_t> &keep, const std::vector<int32_t> &win, const std::vector<uint8_t> &flip,
+           std::string &err) {
     using wclk = std::chrono::steady_clock;
     auto us_since = [](wclk::time_point t) { return (int64_t)std::chrono::duration<double, std::micro>(wclk::now() - t).count(); };
     auto t0 = wclk::now();
@@ -690,6 +699,14 @@ struct FqWriter {
         char *o = text.data() + at[i];
         const size_t hl = (size_t)(c.hoff[i + 1] - c.hoff[i]), wl = (size_t)win[2 * i + 1], wo = (size_t)win[2 * i];
         memcpy(o, c.hdr.data() + c.hoff[i], hl); o += hl; *o++ = '\n';
+        if (!flip.empty() && flip[i]) {
+          const char *se = c.seq.data() + c.off[i + 1] - 1 - wo, *qe = c.qual.data() + c.off[i + 1] - 1 - wo;
+          for (size_t j = 0; j < wl; j++) o[j] = fq_complement(se[-(ptrdiff_t)j]);
+          o += wl; *o++ = '\n'; *o++ = '+'; *o++ = '\n';
+          for (size_t j = 0; j < wl; j++) o[j] = qe[-(ptrdiff_t)j];
+          o += wl; *o++ = '\n';
+          continue;
+        }
         memcpy(o, c.seq.data() + c.off[i] + wo, wl); o += wl; *o++ = '\n'; *o++ = '+'; *o++ = '\n';
         memcpy(o, c.qual.data() + c.off[i] + wo, wl); o += wl; *o++ = '\n';
       }
@@ -736,6 +753,75 @@ struct FqWriter {
   }
 };
 
+// The chunk pipeline of a file-level call (filterAndTrim's and removePrimers'): the inputs are opened, existing outputs removed,
+// and chunk after chunk is parsed on a thread of its own under the verdicts and the writing of the chunk before.
+// verdict(ch, first_chunk, keep, win, flip) settles a chunk: keep[i] (set to 1 on entry), win[k] (offset and length per read of
+// file k) and, for reads to be written as their reverse complement, flip (empty: none); it returns a DADA2HIP_* code with the
+// message in errbuf.  On any failure nothing half written is left behind.  W: where the pipeline's clocks go in `tot`.
+struct FqClockWords { int parse, deflate, write, inflate; };
+template <typename Verdict>
+int fq_run_chunks(int nfile, const char *const *in, const char *const *out, int32_t compress, int64_t chunk_reads, int64_t *tot,
+                  const FqClockWords &W, int64_t &nin, int64_t &nout, Verdict &&verdict, char *errbuf, size_t errlen) {
+  using fclk = std::chrono::steady_clock;
+  auto us_since = [](fclk::time_point t) { return (int64_t)std::chrono::duration<double, std::micro>(fclk::now() - t).count(); };
+  FqSource src[2];
+  FqWriter wr[2];
+  FqChunk chunks[2][2];                                         // [slot][file]: the parser fills one slot while the other is filtered and written
+  std::string err;
+  for (int k = 0; k < nfile; k++) {
+    const auto t_open = fclk::now();                            // (a .gz that libdeflate takes is inflated HERE, in one go)
+    if (!src[k].open(in[k], err)) { set_err(errbuf, errlen, err.c_str()); return DADA2HIP_ERR_INPUT; }
+    tot[W.inflate] += us_since(t_open);
+    wr[k].path = out[k]; wr[k].compress = compress != 0;
+  }
+  for (int k = 0; k < nfile; k++) (void)remove(out[k]);         // :634-640 (writeFastq does not overwrite)
+  nin = 0; nout = 0;
+  std::vector<int32_t> win[2];
+  std::vector<uint8_t> keep, flip;
+  int rc = DADA2HIP_OK;
+  struct Parsed { bool ok; std::string err; int64_t us; };
+  auto parse = [&](int slot) {
+    const auto t_parse = fclk::now();
+    Parsed r{true, std::string(), 0};
+    for (int k = 0; k < nfile && r.ok; k++) r.ok = fq_read_chunk(src[k], chunk_reads, chunks[slot][k], r.err);
+    r.us = us_since(t_parse);
+    return r;
+  };
+  std::future<Parsed> ahead = std::async(std::launch::async, parse, 0);
+  for (int slot = 0;; slot ^= 1) {
+    const bool first = nin == 0;
+    const Parsed got = ahead.get();
+    tot[W.parse] += got.us;
+    if (!got.ok) { set_err(errbuf, errlen, got.err.c_str()); rc = DADA2HIP_ERR_INPUT; break; }
+    FqChunk *ch = chunks[slot];
+    if (nfile == 2 && ch[0].n != ch[1].n) {                     // :966
+      set_err(errbuf, errlen, ("Mismatched forward and reverse sequence files: " + std::to_string(ch[0].n) + ", " + std::to_string(ch[1].n) + ".").c_str());
+      rc = DADA2HIP_ERR_INPUT;
+      break;
+    }
+    const int64_t n = ch[0].n;
+    if (n == 0) break;
+    ahead = std::async(std::launch::async, parse, slot ^ 1);   // the next chunk is read and parsed under this one's kernels and deflate
+    nin += n;
+    keep.assign((size_t)n, 1);
+    flip.clear();
+    rc = verdict(ch, first, keep, win, flip);
+    if (rc != DADA2HIP_OK) break;
+    for (int64_t i = 0; i < n; i++) nout += keep[i];
+    for (int k = 0; k < nfile && rc == DADA2HIP_OK; k++)
+      if (!wr[k].put(ch[k], keep, win[k], flip, err)) { set_err(errbuf, errlen, err.c_str()); rc = DADA2HIP_ERR_RUNTIME; }
+    if (rc != DADA2HIP_OK) break;
+  }
+  if (ahead.valid()) ahead.wait();                              // (a run that stops early still waits for its parser)
+  for (int k = 0; k < nfile; k++) {
+    if (!wr[k].finish(err) && rc == DADA2HIP_OK) { set_err(errbuf, errlen, err.c_str()); rc = DADA2HIP_ERR_RUNTIME; }
+    tot[W.deflate] += wr[k].us_deflate; tot[W.write] += wr[k].us_write;
+  }
+  if (rc != DADA2HIP_OK)                                        // nothing half written is left behind
+    for (int k = 0; k < nfile; k++) (void)remove(out[k]);
+  return rc;
+}
+
 // FS_* of filter_host.h: the words of a call's stats that add up over chunks, and the file level's own
 enum { FQ_US_PARSE = 21, FQ_US_DEFLATE = 22, FQ_US_WRITE = 23, FQ_US_TOTAL = 24, FQ_US_INFLATE = 25 };
 void fq_add_stats(int64_t *tot, const int64_t *st) {
@@ -747,7 +833,6 @@ int filter_files_body(dada2hip_filter *ctx, int nfile, const char *const *in, co
                       const dada2hip_filter_params *const *params, int32_t compress, int64_t chunk_reads, int64_t *reads_in,
                       int64_t *reads_out, int64_t *stats, char *errbuf, size_t errlen) {
   using fclk = std::chrono::steady_clock;
-  auto us_since = [](fclk::time_point t) { return (int64_t)std::chrono::duration<double, std::micro>(fclk::now() - t).count(); };
   const auto t_call = fclk::now();
   if (reads_in) *reads_in = 0;
   if (reads_out) *reads_out = 0;
@@ -764,75 +849,86 @@ int filter_files_body(dada2hip_filter *ctx, int nfile, const char *const *in, co
   }
   if (chunk_reads <= 0) chunk_reads = 100000;                   // filterAndTrim(n = 1e5)
   d2::knobs_reload();
-  FqSource src[2];
-  FqWriter wr[2];
-  FqChunk chunks[2][2];                                         // [slot][file]: the parser fills one slot while the other is filtered and written
   dada2hip_filter_params P[2];
-  std::string err;
+  for (int k = 0; k < nfile; k++) P[k] = *params[k];
   int64_t tot[DADA2HIP_FILTER_NSTATS] = {0}, st[DADA2HIP_FILTER_NSTATS];
-  for (int k = 0; k < nfile; k++) {
-    const auto t_open = fclk::now();                            // (a .gz that libdeflate takes is inflated HERE, in one go)
-    if (!src[k].open(in[k], err)) { set_err(errbuf, errlen, err.c_str()); return DADA2HIP_ERR_INPUT; }
-    tot[FQ_US_INFLATE] += us_since(t_open);
-    P[k] = *params[k];
-    wr[k].path = out[k]; wr[k].compress = compress != 0;
-  }
-  for (int k = 0; k < nfile; k++) (void)remove(out[k]);         // :634-640 (writeFastq does not overwrite)
   int64_t nin = 0, nout = 0;
-  std::vector<int32_t> code[2], win[2];
-  std::vector<uint8_t> keep;
-  int rc = DADA2HIP_OK;
-  struct Parsed { bool ok; std::string err; int64_t us; };
-  auto parse = [&](int slot) {
-    const auto t_parse = fclk::now();
-    Parsed r{true, std::string(), 0};
-    for (int k = 0; k < nfile && r.ok; k++) r.ok = fq_read_chunk(src[k], chunk_reads, chunks[slot][k], r.err);
-    r.us = us_since(t_parse);
-    return r;
-  };
-  std::future<Parsed> ahead = std::async(std::launch::async, parse, 0);
-  for (int slot = 0;; slot ^= 1) {
-    const bool first = nin == 0;
-    const Parsed got = ahead.get();
-    tot[FQ_US_PARSE] += got.us;
-    if (!got.ok) { set_err(errbuf, errlen, got.err.c_str()); rc = DADA2HIP_ERR_INPUT; break; }
-    FqChunk *ch = chunks[slot];
-    if (nfile == 2 && ch[0].n != ch[1].n) {                     // :966
-      set_err(errbuf, errlen, ("Mismatched forward and reverse sequence files: " + std::to_string(ch[0].n) + ", " + std::to_string(ch[1].n) + ".").c_str());
-      rc = DADA2HIP_ERR_INPUT;
-      break;
-    }
+  std::vector<int32_t> code[2];
+  const int rc = fq_run_chunks(nfile, in, out, compress, chunk_reads, tot, FqClockWords{FQ_US_PARSE, FQ_US_DEFLATE, FQ_US_WRITE, FQ_US_INFLATE},
+                               nin, nout,
+                               [&](FqChunk *ch, bool first, std::vector<uint8_t> &keep, std::vector<int32_t> *win, std::vector<uint8_t> &) -> int {
     const int64_t n = ch[0].n;
-    if (n == 0) break;
-    ahead = std::async(std::launch::async, parse, slot ^ 1);   // the next chunk is read and parsed under this one's kernels and deflate
-    nin += n;
-    keep.assign((size_t)n, 1);
-    for (int k = 0; k < nfile && rc == DADA2HIP_OK; k++) {
+    for (int k = 0; k < nfile; k++) {
       if (first && P[k].qual_offset == 0) P[k].qual_offset = fq_auto_offset(ch[k]);
       code[k].resize((size_t)n); win[k].resize(2 * (size_t)n);
-      rc = dada2hip_filter_reads(ctx, n, ch[k].seq.data(), ch[k].qual.data(), ch[k].off.data(), &P[k], code[k].data(), win[k].data(),
-                                 nullptr, nullptr, nullptr, nullptr, st, errbuf, errlen);
-      if (rc != DADA2HIP_OK) break;
+      const int r = dada2hip_filter_reads(ctx, n, ch[k].seq.data(), ch[k].qual.data(), ch[k].off.data(), &P[k], code[k].data(), win[k].data(),
+                                          nullptr, nullptr, nullptr, nullptr, st, errbuf, errlen);
+      if (r != DADA2HIP_OK) return r;
       if (k == 0) fq_add_stats(tot, st);
       else for (int i = 15; i <= 20; i++) tot[i] += st[i];     // (the verdict counts are the forward reads'; the clocks are both files')
       for (int64_t i = 0; i < n; i++) if (code[k][i] != 0) keep[i] = 0;
     }
-    if (rc != DADA2HIP_OK) break;
-    for (int64_t i = 0; i < n; i++) nout += keep[i];
-    for (int k = 0; k < nfile && rc == DADA2HIP_OK; k++)
-      if (!wr[k].put(ch[k], keep, win[k], err)) { set_err(errbuf, errlen, err.c_str()); rc = DADA2HIP_ERR_RUNTIME; }
-    if (rc != DADA2HIP_OK) break;
+    return DADA2HIP_OK;
+  }, errbuf, errlen);
+  if (rc != DADA2HIP_OK) return rc;
+  tot[0] = nin; tot[1] = nout;
+  tot[FQ_US_TOTAL] = (int64_t)std::chrono::duration<double, std::micro>(fclk::now() - t_call).count();
+  if (reads_in) *reads_in = nin;
+  if (reads_out) *reads_out = nout;
+  if (stats) memcpy(stats, tot, sizeof tot);
+  return DADA2HIP_OK;
+}
+
+// removePrimers' file level (R/filter.R:116-225): dada2hip_primers_reads per chunk, the kept windows written in the kept
+// orientation, and the whole-file rule (:157-158) at the end - it asks for the matches of the reads AS GIVEN, summed over the file
+enum { PQ_HITS_FWD = 8, PQ_HITS_REV = 9, PQ_US_PARSE = 16, PQ_US_DEFLATE = 17, PQ_US_WRITE = 18, PQ_US_TOTAL = 19, PQ_US_INFLATE = 20 };
+int primers_file_body(const char *in, const char *out, const dada2hip_primer_params *params, int32_t compress, int64_t chunk_reads,
+                      int32_t device, int64_t *reads_in, int64_t *reads_out, int64_t *stats, char *errbuf, size_t errlen) {
+  using fclk = std::chrono::steady_clock;
+  const auto t_call = fclk::now();
+  if (reads_in) *reads_in = 0;
+  if (reads_out) *reads_out = 0;
+  if (!in || !out || !params) { set_err(errbuf, errlen, "File paths must be provided in character format."); return DADA2HIP_ERR_INPUT; }
+  if (strcmp(in, out) == 0) { set_err(errbuf, errlen, "Output files must be distinct from the input files."); return DADA2HIP_ERR_INPUT; }   // :102
+  if (chunk_reads <= 0) chunk_reads = 100000;
+  d2::knobs_reload();
+  int64_t tot[DADA2HIP_PRIMERS_NSTATS] = {0}, st[DADA2HIP_PRIMERS_NSTATS];
+  int64_t nin = 0, nout = 0;
+  std::vector<int32_t> code, flip32, first, last;
+  int rc = fq_run_chunks(1, &in, &out, compress, chunk_reads, tot, FqClockWords{PQ_US_PARSE, PQ_US_DEFLATE, PQ_US_WRITE, PQ_US_INFLATE}, nin, nout,
+                         [&](FqChunk *ch, bool, std::vector<uint8_t> &keep, std::vector<int32_t> *win, std::vector<uint8_t> &flip) -> int {
+    const int64_t n = ch[0].n;
+    code.resize((size_t)n); flip32.resize((size_t)n); first.resize((size_t)n); last.resize((size_t)n);
+    win[0].assign(2 * (size_t)n, 0); flip.assign((size_t)n, 0);
+    const int r = dada2hip_primers_reads(n, ch[0].seq.data(), ch[0].off.data(), params, device, code.data(), flip32.data(), first.data(),
+                                         last.data(), nullptr, nullptr, st, errbuf, errlen);
+    if (r != DADA2HIP_OK) {
+      if (r == DADA2HIP_ERR_UNSUPPORTED) {                      // a letter that is no IUPAC code: name the record, not its number in the chunk
+        for (int64_t i = 0; i < n; i++)
+          if (code[i] == 4) {
+            const std::string id(ch[0].hdr.data() + ch[0].hoff[i], (size_t)(ch[0].hoff[i + 1] - ch[0].hoff[i]));
+            set_err(errbuf, errlen, ("dada2hip: read " + std::to_string(nin - n + i + 1) + " (" + id +
+                                     ") holds a letter outside the upper-case IUPAC codes ACGTMRWSYKVHDBN.").c_str());
+            break;
+          }
+      }
+      return r;
+    }
+    for (int i = 0; i < PQ_US_PARSE; i++) tot[i] += st[i];
+    for (int64_t i = 0; i < n; i++) {
+      if (code[i] != 0) { keep[i] = 0; continue; }
+      win[0][2 * i] = first[i] - 1; win[0][2 * i + 1] = last[i] - first[i] + 1;   // :213 narrow(fq, first, last)
+      flip[i] = (uint8_t)flip32[i];
+    }
+    return DADA2HIP_OK;
+  }, errbuf, errlen);
+  if (rc != DADA2HIP_OK) return rc;
+  if (tot[PQ_HITS_FWD] == 0 || (params->primer_rev && tot[PQ_HITS_REV] == 0)) {   // :157-158
+    (void)remove(out);
+    nout = 0;
   }
-  if (ahead.valid()) ahead.wait();                              // (a run that stops early still waits for its parser)
-  for (int k = 0; k < nfile; k++) {
-    if (!wr[k].finish(err) && rc == DADA2HIP_OK) { set_err(errbuf, errlen, err.c_str()); rc = DADA2HIP_ERR_RUNTIME; }
-    tot[FQ_US_DEFLATE] += wr[k].us_deflate; tot[FQ_US_WRITE] += wr[k].us_write;
-  }
-  if (rc != DADA2HIP_OK) {                                      // nothing half written is left behind
-    for (int k = 0; k < nfile; k++) (void)remove(out[k]);
-    return rc;
-  }
-  tot[0] = nin; tot[1] = nout; tot[FQ_US_TOTAL] = us_since(t_call);
+  tot[0] = nin; tot[1] = nout;
+  tot[PQ_US_TOTAL] = (int64_t)std::chrono::duration<double, std::micro>(fclk::now() - t_call).count();
   if (reads_in) *reads_in = nin;
   if (reads_out) *reads_out = nout;
   if (stats) memcpy(stats, tot, sizeof tot);
@@ -870,6 +966,13 @@ int dada2hip_filter_fastq_paired(dada2hip_filter *ctx, const char *in_f, const c
   const dada2hip_filter_params *params[2] = {params_f, params_r};
   return filter_files_guarded(errbuf, errlen, [&] {
     return filter_files_body(ctx, 2, in, out, params, compress, chunk_reads, reads_in, reads_out, stats, errbuf, errlen);
+  });
+}
+
+int dada2hip_primers_fastq(const char *in, const char *out, const dada2hip_primer_params *params, int32_t compress, int64_t chunk_reads,
+                           int32_t device, int64_t *reads_in, int64_t *reads_out, int64_t *stats, char *errbuf, size_t errlen) {
+  return filter_files_guarded(errbuf, errlen, [&] {
+    return primers_file_body(in, out, params, compress, chunk_reads, device, reads_in, reads_out, stats, errbuf, errlen);
   });
 }
 

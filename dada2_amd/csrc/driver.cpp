@@ -3568,6 +3568,9 @@ int dada2hip_nwalign(const char *s1, const char *s2, int32_t match, int32_t mism
 // ---- filterAndTrim: the per-read verdicts of R/filter.R:613-730 and the phiX screen (src/filter.cpp) ----
 #include "filter_host.h"
 
+// ---- removePrimers: primer search on both strands, orientation and the kept window (R/filter.R:81-233) ----
+#include "primers_host.h"
+
 // ---- result getters ------------------------------------------------------------------------------
 int32_t dada2hip_result_nclust(const dada2hip_result *r) { return r->nclust; }
 int32_t dada2hip_result_nraw(const dada2hip_result *r) { return r->nraw; }

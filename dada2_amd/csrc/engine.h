@@ -647,6 +647,29 @@ void launch_filter_ee(const FilterArgs &A, int n, const uint8_t *d_qual, const l
 // counts[r][4^k]: the k-mers of the kept window that are A/C/G/T only, first letter most significant (oligonucleotideFrequency's order)
 void launch_filter_kmers(int n, int k, const uint8_t *d_seq, const long long *d_off, const FilterOut *d_out, int32_t *d_counts,
                          hipStream_t st);
+// removePrimers (primers.inc.hip).  A batch is n reads: the bytes of read r are seq[off[r] .. off[r + 1]).  Four patterns are searched
+// in the read as given: 0 the forward primer, 1 the reverse primer, 2 and 3 the reverse complements of the two (a match of P on the
+// read's reverse complement at start st is a match of rc(P) on the read at n - L - st).  A pattern letter is a byte of plane
+// selectors: bits 0-3 the planes "the read's IUPAC letter holds A / C / G / T" (the non-fixed rule: the sets intersect), bits 4-7
+// the planes "the read's letter IS A / C / G / T" (the fixed rule: equal bytes).
+constexpr int PR_THREADS = 128;               // two waves per read: a 1 500-nt read with four patterns is 96 lane tasks
+constexpr int PR_MAXL = 128;                  // letters of a primer
+constexpr int PR_MAXMM = 15;                  // mismatches: the counter has at most four bit planes
+constexpr int PR_TILE_MAX = 64;               // chunks of 64 starts per tile of a read (DADA2HIP_PRIMERS_TILE: fewer)
+constexpr int PR_GRID = 4096;                 // blocks of a launch; a block takes reads blockIdx.x, + gridDim.x, ...
+constexpr int32_t PR_NA = INT32_MIN;          // a start of a pattern that has no match
+struct PrimerArgs {
+  uint8_t sel[4][PR_MAXL];
+  int32_t len[4];                             // letters of pattern k
+  int32_t act[4], nact;                       // the patterns searched, in order
+  int32_t mm, nbits, has_rev, orient, trim_fwd, trim_rev, tile;
+};
+// code: 0 kept, 1 no forward primer, 2 no reverse primer, 3 nothing left (last > first is false), 4 a letter that is no IUPAC code;
+// first / last: the kept window, 1-based and inclusive, in the kept orientation; hits: fwd, rev, fwd on rc, rev on rc
+struct PrimerOut { int32_t code, flip, first, last, hits[4]; };
+// starts (optional): [r * 8 + 2 k], [+ 1] the first and the last start of pattern k, 1-based on the strand it stands for
+void launch_primers(const PrimerArgs &A, int n, const uint8_t *d_seq, const long long *d_off, PrimerOut *d_out, int32_t *d_starts,
+                    hipStream_t st);
 void launch_calc_pA(int n, const int32_t *d_reads, const double *d_E, const uint8_t *d_prior, double *d_out,
                     hipStream_t st);
 

@@ -72,6 +72,9 @@ struct Knobs {
   long long tax_chunk = 0;            // DADA2HIP_TAX_CHUNK=n           ... queries per chunk of a pass (at least 1; at most, and unset, what keeps the per-tile records within 64 MB)
   long long filter_piece = 0;         // DADA2HIP_FILTER_PIECE=n        filterAndTrim: reads per piece of a call (at least 1; at most, and unset, 65 536)
   long long filter_piece_bytes = 0;   // DADA2HIP_FILTER_PIECE_BYTES=n  ... bases per piece (at least 1; at most, and unset, 32 MiB; a longer read is a piece of its own)
+  long long primers_piece = 0;        // DADA2HIP_PRIMERS_PIECE=n       removePrimers: reads per piece of a call (at least 1; at most, and unset, 65 536)
+  long long primers_piece_bytes = 0;  // DADA2HIP_PRIMERS_PIECE_BYTES=n ... bases per piece (at least 1; at most, and unset, 32 MiB; a longer read is a piece of its own)
+  long long primers_tile = 0;         // DADA2HIP_PRIMERS_TILE=n        ... chunks of 64 match starts per tile of a read (at least 1; at most, and unset, 64)
   int species_cand = 1 << 20;         // DADA2HIP_SPECIES_CAND=n        assignSpecies: records of the candidate buffer and of the hit buffer (a launch that counts more is re-run in pieces)
   int species_chunk = 8192;           // DADA2HIP_SPECIES_CHUNK=n       ... distinct queries per pass over the references (at most 8 192: the presence bitmap is sized for it)
   bool derep_zlib = false;           // DADA2HIP_DEREP_INFLATE=zlib    .gz files through zlib's streaming inflate even where libdeflate is installed
@@ -132,6 +135,7 @@ struct Knobs {
     k.tax_slab = I("DADA2HIP_TAX_SLAB", 256);
     auto P = [&](const char *n) -> long long { const char *e = S(n); return e ? std::max(1ll, std::atoll(e)) : 0ll; };   // a size: 0 = unset
     k.tax_chunk = P("DADA2HIP_TAX_CHUNK"); k.filter_piece = P("DADA2HIP_FILTER_PIECE"); k.filter_piece_bytes = P("DADA2HIP_FILTER_PIECE_BYTES");
+    k.primers_piece = P("DADA2HIP_PRIMERS_PIECE"); k.primers_piece_bytes = P("DADA2HIP_PRIMERS_PIECE_BYTES"); k.primers_tile = P("DADA2HIP_PRIMERS_TILE");
     k.species_cand = I("DADA2HIP_SPECIES_CAND", 1 << 20); k.species_chunk = I("DADA2HIP_SPECIES_CHUNK", 8192);
     if (const char *e = S("DADA2HIP_DEREP_INFLATE")) k.derep_zlib = !std::strcmp(e, "zlib");
     if (const char *e = S("DADA2HIP_DEREP_TIMES")) k.derep_times = !std::strcmp(e, "1");

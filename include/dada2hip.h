@@ -24,6 +24,7 @@
  *   dada2hip_derep_*        <- derepFastq() / qtables2()  R/sequenceIO.R:45-124, :150-183 (host-side C++, zlib)
  *   dada2hip_filter_*       <- filterAndTrim() / fastqFilter() / fastqPairedFilter() / isPhiX() / seqComplexity()  R/filter.R:402-1275 on
  *                              C_matchRef / C_matrixEE (src/filter.cpp:7-49)
+ *   dada2hip_primers_*      <- removePrimers()  R/filter.R:81-233 (vmatchPattern without indels, restated)
  *
  * Conventions: plain C, no exceptions cross the boundary.  Every call returns 0 on success or a
  * non-zero code with a NUL-terminated message in `errbuf` (the reference's Rcpp::stop texts are
@@ -58,6 +59,9 @@
  *   DADA2HIP_SPECIES_CHUNK=<n>         ... distinct queries per pass over the references (default and at most 8 192)
  *   DADA2HIP_FILTER_PIECE=<n>          dada2hip_filter_reads: reads per piece of a call (at least 1; default and at most 65 536)
  *   DADA2HIP_FILTER_PIECE_BYTES=<n>    ... bases per piece (at least 1; default and at most 32 MiB; a longer read is a piece of its own)
+ *   DADA2HIP_PRIMERS_PIECE=<n>         dada2hip_primers_reads: reads per piece of a call (at least 1; default and at most 65 536)
+ *   DADA2HIP_PRIMERS_PIECE_BYTES=<n>   ... bases per piece (at least 1; default and at most 32 MiB; a longer read is a piece of its own)
+ *   DADA2HIP_PRIMERS_TILE=<n>          ... chunks of 64 match starts per tile of a read (at least 1; default and at most 64)
  *   DADA2HIP_PROFILE=1, DADA2HIP_V2_SUMMARY, DADA2HIP_V2_DEBUG   per-launch device times in the stats; traces on stderr
  * Test / tuning knobs (sizes of rings and grids, forced growth paths, injected failures) are listed with their meaning in
  * knobs.h and DESIGN.md §10b; they are not part of the interface.
@@ -540,6 +544,49 @@ int dada2hip_filter_fastq_paired(dada2hip_filter *ctx, const char *in_f, const c
                                  const dada2hip_filter_params *params_f, const dada2hip_filter_params *params_r, int32_t compress,
                                  int64_t chunk_reads, int64_t *reads_in, int64_t *reads_out, int64_t *stats, char *errbuf,
                                  size_t errlen);
+
+/* ---- removePrimers: primer search on both strands, orientation and trimming (R/filter.R:81-233) ----------------------------------
+ * A match of a primer of L letters in a read of n letters is a start st (0-based here, reported 1-based) at which at most
+ * max_mismatch of the positions st .. st + L - 1 mismatch; st runs over -max_mismatch .. n - L + max_mismatch and a position outside
+ * the read is a mismatch (vmatchPattern(primer, reads, max.mismatch, with.indels = FALSE) with its "out of limits" matches, as
+ * documented; DESIGN.md §8e says what of this is unverified).  A primer of upper-case A/C/G/T only is matched byte for byte (fixed
+ * = TRUE: an N in the read mismatches); any other primer by IUPAC sets, both letters read as sets over {A,C,G,T} that match when
+ * they intersect.  The forward primer uses its FIRST match, the reverse primer its LAST (:159-177).  With orient the same searches
+ * run on the read's reverse complement (A<->T C<->G M<->K R<->Y V<->B H<->D; W S N themselves), and a read is flipped only when it
+ * has no forward match as given and at least one on its reverse complement (:181).  In the kept orientation a read needs a forward
+ * match and, if primer_rev is given, a reverse match (:192-194); first = end of the forward match + 1 if trim_fwd else 1, last =
+ * start of the reverse match - 1 if primer_rev && trim_rev else n, and the read is kept when last > first, strictly (:201-211).
+ * code: 0 kept, 1 no forward primer, 2 no reverse primer, 3 nothing left, 4 a letter outside the fifteen upper-case IUPAC codes.
+ * Refused with DADA2HIP_ERR_UNSUPPORTED: allow_indels != 0, a primer of more than 128 letters, max_mismatch above 15 or not below
+ * a primer's length, a primer or read letter outside ACGTMRWSYKVHDBN (the message names the read).
+ * dada2hip_primers_reads: n reads, read r being seq[offsets[r] .. offsets[r + 1]).  Outputs (each optional): code[n], flip[n],
+ * first[n], last[n] (1-based, inclusive, in the kept orientation; 0 for codes 1, 2 and 4); hits[4 r + k] the matches of k = 0 the
+ * forward primer, 1 the reverse primer, 2 the forward primer on the reverse complement, 3 the reverse primer on it (2 and 3 are 0
+ * without orient); starts[8 r + 2 k], [+ 1] the first and the last start of k, 1-based on the strand k stands for, INT32_MIN
+ * without a match.  It applies no whole-file rule.
+ * dada2hip_primers_fastq: a FASTQ file (plain or gzip) into `out`, in chunks of chunk_reads records (<= 0: 100 000), with the reader,
+ * the writer and the gzip members of dada2hip_filter_fastq.  A kept record is `@id`, letters first..last, `+`, their qualities; of
+ * a flipped read the reverse complement's letters and the reversed qualities.  The whole-file rule (:157-158) is applied at the
+ * end: when no read of the file has a forward match AS GIVEN (or, with primer_rev, none a reverse match as given), what was written
+ * is removed and reads_out is 0, even where orient would have flipped every read.  in == out is DADA2HIP_ERR_INPUT; an existing
+ * `out` is removed first; no file is left when nothing passes or the call fails.
+ * stats (optional, DADA2HIP_PRIMERS_NSTATS int64 words): [0] reads in, [1] reads kept, [2..5] reads with code 1..4, [6] reads
+ * flipped, [7] reads with more than one match of a pattern (the reference's "Multiple matches" message), [8] and [9] the forward
+ * and the reverse primer's matches on the reads as given, summed, [10] pieces, [11] tiles, [12] bytes copied to the device,
+ * [13] host microseconds of the upload, [14] device microseconds of the kernel, [15] host microseconds of the download, [16] of
+ * parsing, [17] of deflate, [18] of writing, [19] of the whole call, [20] of opening the input. */
+#define DADA2HIP_PRIMERS_NSTATS 24
+typedef struct dada2hip_primer_params {
+  const char *primer_fwd;
+  const char *primer_rev;          /* NULL: none */
+  int32_t max_mismatch, trim_fwd, trim_rev, orient, allow_indels, reserved;
+} dada2hip_primer_params;
+int dada2hip_primers_reads(int64_t n, const char *seq, const int64_t *offsets, const dada2hip_primer_params *params, int32_t device,
+                           int32_t *code, int32_t *flip, int32_t *first, int32_t *last, int32_t *hits, int32_t *starts,
+                           int64_t *stats, char *errbuf, size_t errlen);
+int dada2hip_primers_fastq(const char *in, const char *out, const dada2hip_primer_params *params, int32_t compress,
+                           int64_t chunk_reads, int32_t device, int64_t *reads_in, int64_t *reads_out, int64_t *stats,
+                           char *errbuf, size_t errlen);
 
 /* One b_compare round exposed for kernel-level parity tests and for bench.py's roofline leg:
  * compares every unique of `s` against unique `centre` exactly as CompareParallel does
