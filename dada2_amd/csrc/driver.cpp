@@ -123,6 +123,7 @@ struct dada2hip_sample {
   NwScratch scr;
   int scr_class = -1, scr_band = 0;
   size_t scr_items = 0;          // alignments per launch the lane-kernel scratch was sized for
+  long long scr_ring = 0;        // ... and the DADA2HIP_NW_RING it was built under (0 = unset)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::shared_ptr<void> run_cache;   // Run object: partition-state buffers reused by every dada2hip_sample_run
 };
@@ -529,13 +530,18 @@ void ensure_scratch(dada2hip_sample *s, int band, size_t items = 0, bool force_g
   SampleDev &D = s->D;
   int wc = force_generic ? 0 : nw_class(band, D.maxlen, D.minlen);
   const size_t want = std::max<size_t>((size_t)D.N, items);
-  if (s->scr_class == wc && s->scr_band == band && s->scr.ptr && s->scr_items >= want) return;
+  const long long ring = knobs().nw_ring;   // DADA2HIP_NW_RING: a ring built under another value is built again
+  if (s->scr_class == wc && s->scr_band == band && s->scr.ptr && s->scr_items >= want && s->scr_ring == ring) return;
   s->scr_items = want;
+  s->scr_ring = ring;
   size_t ppw = nw_ptr_words_per_wave(wc, band, D.maxlen, D.minlen);
   int nwaves = (int)std::min<size_t>(4096, ((want + 63) / 64 + 3) & ~(size_t)3);
   const size_t budget_words = (size_t)6 << 28;  // 6 GiB of pointer scratch at most
   while (nwaves > 64 && (size_t)nwaves * ppw > budget_words) nwaves /= 2;
   nwaves = std::max(4, nwaves & ~3);
+  // the test knob: fewer waves than the automatic size (a multiple of 4, at least 4), so that a launch of a few hundred
+  // alignments gives every wave a second and a third chunk in the slot it has used (launch_nw caps its grid at the ring)
+  if (ring > 0) nwaves = (int)std::min<long long>(nwaves, std::max<long long>(4, ring & ~3ll));
   s->scr.nwaves = nwaves;
   s->scr.ptr_words_per_wave = ppw;
   s->scr.t_words_per_wave = (size_t)((D.maxlen + 7) / 8) * 64;
@@ -3173,6 +3179,8 @@ int32_t dada2hip_launch_ledger(uint64_t *mask, int32_t nwords, int32_t clear) {
   for (int i = 0; i < nwords && mask; i++) mask[i] = i < LEDGER_WORDS ? w[i] : 0;
   return LEDGER_WORDS;
 }
+
+int32_t dada2hip_nw_ring_trips(int32_t clear) { return nw_trips_read(clear != 0); }
 
 int dada2hip_calc_pA(int32_t n, const int32_t *reads, const double *E_reads, const uint8_t *prior, int32_t device,
                      double *out, char *errbuf, size_t errlen) {

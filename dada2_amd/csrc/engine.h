@@ -220,6 +220,10 @@ enum {
 };
 void ledger_note(int bit);
 void ledger_read(uint64_t *out, bool clear);
+// ... and, in the same style (one relaxed atomic max per launch_nw, host side only): the most trips through the chunk loop
+// (`chunk += nwaves`) a lane launch was sized for - ceil(chunks / waves launched), chunks from the host's bound on the work
+void nw_trips_note(int trips);
+int nw_trips_read(bool clear);
 void launch_pair_class(const SampleDev &S, const int32_t *d_pc, const int32_t *d_pr, int n, const ScreenParams &sp,
                        uint8_t *d_out, hipStream_t st);
 

@@ -28,6 +28,14 @@ void ledger_read(uint64_t *out, bool clear) {
   for (int w = 0; w < LEDGER_WORDS; w++)
     out[w] = clear ? g_ledger[w].exchange(0, std::memory_order_relaxed) : g_ledger[w].load(std::memory_order_relaxed);
 }
+// ... and the most trips through its chunk loop a lane launch (launch_nw) was sized for: ceil(chunks / waves launched), chunks
+// from the host's bound on the work.  From 2 on a wave uses its slot of the scratch ring again (dada2hip_nw_ring_trips)
+static std::atomic<int32_t> g_nw_trips{0};
+void nw_trips_note(int trips) {
+  int32_t cur = g_nw_trips.load(std::memory_order_relaxed);
+  while (cur < trips && !g_nw_trips.compare_exchange_weak(cur, trips, std::memory_order_relaxed)) {}
+}
+int nw_trips_read(bool clear) { return clear ? g_nw_trips.exchange(0, std::memory_order_relaxed) : g_nw_trips.load(std::memory_order_relaxed); }
 
 static __device__ __forceinline__ uint32_t base_at(const uint32_t *__restrict__ row, int p) {
   return (row[p >> 4] >> ((p & 15) << 1)) & 3u;
@@ -2100,6 +2108,7 @@ void launch_nw(const SampleDev &S, int wclass, int centre, const int32_t *d_chun
   int grid = (waves + 3) / 4;
   if (grid * 4 > scr.nwaves) grid = scr.nwaves / 4;
   if (grid < 1) grid = 1;
+  nw_trips_note(((maxwork + 63) / 64 + grid * 4 - 1) / (grid * 4));
   NwArgs a;
   memset(&a, 0, sizeof a);
   a.S = S; a.centre = centre; a.chunk_centre = d_chunk_centre; a.pair_centre = d_pair_centre; a.work = d_work; a.nwork_dev = d_nwork;

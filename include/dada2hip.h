@@ -44,6 +44,8 @@
  * The library SETS one variable when it is loaded, unless the caller has: GPU_MAX_HW_QUEUES=8 (the HIP runtime's hardware queues
  * per process, 4 by default; a run uses three streams, several samples in flight three each).
  *   DADA2HIP_NW_KERNEL=lane|coop|wide  force one aligner family;  DADA2HIP_AD_HOMO=0  homopolymer gaps on the lane kernels
+ *   DADA2HIP_NW_RING=<n>               waves of the lane aligners' scratch ring (a multiple of 4, at least 4; default and at most
+ *                                      the automatic size: 4 096 waves, halved down to 64 while the pointers would pass 6 GiB)
  *   DADA2HIP_WAIT=block, DADA2HIP_WAIT_TIMEOUT_S=<s>   sleep instead of spin while waiting; bound of every device wait
  *   DADA2HIP_HOST_THREADS=<n>, DADA2HIP_ALLOC_CACHE=0, DADA2HIP_ALLOC_CACHE_GB=<n>   marshalling pool, allocation cache
  *   DADA2HIP_DEREP_INFLATE=zlib        dada2hip_derep_fastq, dada2hip_filter_fastq: .gz files through zlib's streaming inflate even where libdeflate is installed
@@ -611,6 +613,14 @@ int dada2hip_sample_compare(dada2hip_sample *s, int32_t centre, const double *er
  *  88 + p                      k_nw_gen, p = 1 with a centre per pair
  *  96, 97                      k_gapless, k_gapless_batch */
 int32_t dada2hip_launch_ledger(uint64_t *mask, int32_t nwords, int32_t clear);
+
+/* Diagnostic, beside the ledger and in its style (host side, one relaxed atomic max per launch; no device work, no effect on any
+ * result): the most trips through its chunk loop any launch of the lane aligners (k_nw<WMAX>, k_nw_gen) was sized for since
+ * the last clear - ceil(chunks of 64 alignments / waves launched).  The chunks come from the host's bound on the launch's work:
+ * the count itself for the pair-form calls (nwvec, nwalign, merge, collapse, the bimera table) and for a compare with the k-mer
+ * screen off, the number of uniques where the device counts the work.  1: every wave had one chunk at most; from 2 on a wave
+ * went back to the slot of the scratch ring it had used (DADA2HIP_NW_RING makes the ring small).  Clears when clear != 0. */
+int32_t dada2hip_nw_ring_trips(int32_t clear);
 
 /* Poisson tail used for the abundance p-value: calc_pA (src/pval.cpp:44-64) evaluated by the
  * device kernel for n (reads, E) pairs — for parity tests against the oracle. */

@@ -75,6 +75,41 @@ def read_ledger(clear=True):
     return int(m[0]) | (int(m[1]) << 64)
 
 
+def read_ring_trips(clear=True):
+    """dada2hip_nw_ring_trips: the most trips through its chunk loop a lane launch was sized for since the last clear."""
+    from dada2_amd import _lib
+    return int(_lib.lib().dada2hip_nw_ring_trips(int(clear)))
+
+
+RING_WAVES = 4          # the ring the wrap tests ask for: 4 waves = 256 alignments per trip
+RING_MIN_WORK = 513     # ... and the least work of a launch under it: a third trip for some waves
+
+
+class ring(object):
+    """with ring(4): DADA2HIP_NW_RING for the calls inside (the library reads its knobs at every boundary call); ring(None): unset."""
+
+    def __init__(self, waves):
+        self.waves = waves
+
+    def __enter__(self):
+        import os
+        self.old = os.environ.get("DADA2HIP_NW_RING")
+        if self.waves is None:
+            os.environ.pop("DADA2HIP_NW_RING", None)
+        else:
+            os.environ["DADA2HIP_NW_RING"] = str(self.waves)
+        read_ring_trips()
+        return self
+
+    def __exit__(self, *exc):
+        import os
+        if self.old is None:
+            os.environ.pop("DADA2HIP_NW_RING", None)
+        else:
+            os.environ["DADA2HIP_NW_RING"] = self.old
+        return False
+
+
 def describe(mask):
     names = instance_names()
     return [names.get(1 << b, "bit %d" % b) for b in range(128) if (mask >> b) & 1 and not (GAPLESS_BITS >> b) & 1]
@@ -342,8 +377,10 @@ def seeded_err(rng, qmax):
     return e
 
 
-def build(case, lean=False):
-    """The sample of a geometry case.  lean: fewer reads per class (the emulator / the reference check)."""
+def build(case, lean=False, grow=0):
+    """The sample of a geometry case.  lean: fewer reads per class (the emulator / the reference check).  grow: every centre
+    gets lightly changed copies of itself on top (substitutions, an indel in every other one, lengths over the sample's range)
+    until the sample has `grow` uniques per centre - the ring's wrap needs more than 512 alignments in one launch."""
     from helpers import tperr1
     rng = np.random.default_rng(case.seed)
     maxlen, minlen = case.maxlen, case.maxlen - case.diff
@@ -368,6 +405,13 @@ def build(case, lean=False):
         for kind, s in _reads_of(rng, c, case.band, minlen, maxlen, lean, case.gapruns):
             seqs.append(s)
             kinds.append("c%d:%s" % (ci, kind))
+        for k in range(grow if not (big and ci > 0) else 0):
+            s = _sub(rng, c, rng.choice(len(c), size=1 + k % 6, replace=False))
+            if k % 2:
+                p = int(rng.integers(1, len(s) - 1))
+                s = s[:p] + s[p + 1:] if k % 4 == 1 else s[:p] + "ACGT"[int(rng.integers(0, 4))] + s[p:]
+            seqs.append(_fit(rng, s, (minlen, maxlen, int(rng.integers(minlen, maxlen + 1)), len(c))[k % 4]))
+            kinds.append("c%d:grown%d" % (ci, k % 4))
     keep = {}
     for i, s in enumerate(seqs):
         keep.setdefault(s, i)
@@ -434,6 +478,184 @@ def run_case(api, oracle, case, lean=False):
         else:
             os.environ["DADA2HIP_NW_KERNEL"] = old
     return npairs, got
+
+
+RING_GROW = 200        # uniques added per centre: 600 and more in a sample of three centres, 400 and more with two
+
+
+def ring_cases(small_only=False):
+    """The lane cases of every class (plain, generic-score and homopolymer forms) and the unbanded ones: the cases of the wrap."""
+    return [c for c in aligner_cases() if c.name.startswith("lane_") and (c.small or not small_only)]
+
+
+def run_ring_case(api, oracle, case, lean=False):
+    """The case's sample grown past 512 uniques, every one of them aligned with each centre (k-mer cutoff 1, GAPLESS off, no skip
+    mask: the launch's work is the sample) under a scratch ring of four waves: three trips by dada2hip_nw_ring_trips, every pair
+    against the oracle as run_case does (lambda bit-equal, hamming equal), and the same compare with the knob unset - one trip,
+    the same bits.  The resident sample's ring is rebuilt at every change of the knob.  One centre per launch (no chunk_centre,
+    no view): the cases cover stale slots and second-trip indices, not a per-chunk centre.  Returns (pairs compared, ledger)."""
+    import os
+    b = build(case, lean, grow=RING_GROW if case.diff else RING_GROW * 3 // 2)
+    if len(b.seqs) % 64 == 0:                       # (the last chunk is to be ragged: without the last grown read)
+        b = b._replace(seqs=b.seqs[:-1], kinds=b.kinds[:-1], quals=b.quals[:-1], abundances=b.abundances[:-1], skip=b.skip[:-1])
+    n = len(b.seqs)
+    assert n >= RING_MIN_WORK and n % 64 and max(b.centres) < n, (case.name, n)
+    old = os.environ.get("DADA2HIP_NW_KERNEL")
+    os.environ["DADA2HIP_NW_KERNEL"] = case.route
+    npairs = 0
+    try:
+        smp = api.Sample(b.seqs, b.abundances, None, b.quals)
+        try:
+            read_ledger()
+            for ci in b.centres:
+                with ring(RING_WAVES):
+                    lam, ham, cls, st = smp.compare(ci, b.err, b.opts, kdist_cutoff=1.0)
+                    trips = read_ring_trips()
+                assert st["nnw"] == n and st["ngapless"] == 0 and st["nshroud"] == 0, (case.name, st["nnw"], n)
+                assert trips == -(-(-(-n // 64)) // RING_WAVES) >= 3, (case.name, n, "the launch was sized for", trips, "trips: DADA2HIP_NW_RING ignored?")
+                with ring(None):
+                    lam0, ham0, cls0, _ = smp.compare(ci, b.err, b.opts, kdist_cutoff=1.0)
+                    assert read_ring_trips() == 1, case.name
+                same = (np.asarray(lam).view(np.uint64) == np.asarray(lam0).view(np.uint64)) & (np.asarray(ham) == np.asarray(ham0)) & (np.asarray(cls) == np.asarray(cls0))
+                assert same.all(), (case.name, ci, "the ring's size changed unique", int(np.flatnonzero(~same)[0]))
+                L1 = len(b.seqs[ci])
+                for i in range(n):
+                    wl, wh, _, _ = oracle.compare(b.seqs[ci], b.quals[ci, :L1], b.seqs[i], b.quals[i, : len(b.seqs[i])], b.err, b.opts, kdist_cutoff=1.0)
+                    if not (cls[i] == 3 and int(ham[i]) == wh and lam[i] == wl):
+                        raise AssertionError(mismatch_report(oracle, b, ci, i, lam[i], int(ham[i]), wl, wh, read_ledger(False)))
+                    npairs += 1
+            got = read_ledger() & ~GAPLESS_BITS
+            assert got == case.expect, (case.name, "ran", describe(got), "expected", describe(case.expect))
+        finally:
+            smp.close()
+    finally:
+        if old is None:
+            os.environ.pop("DADA2HIP_NW_KERNEL", None)
+        else:
+            os.environ["DADA2HIP_NW_KERNEL"] = old
+    return npairs, got
+
+
+def run_ring_bimera(api, oracle, n=600, L=120):
+    """api.bimera_pairs on n pairs of helpers.bimera_pair_cases under DADA2HIP_NW_KERNEL=lane (k_nw with its move strings kept,
+    k_bimera_lr behind it) and a ring of four waves, under every option set of helpers.BIMERA_PAIR_OPTIONS against the oracle.
+    The export gives every pair a chunk of its own (one query per chunk, 63 empty slots): n chunks on four waves, the chunk's
+    query read through chunk_centre (no view is passed: view_by_chunk is run_ring_whole_path's).  The ledger shows lane instances only; the call with the knob unset gives the same rows
+    (its own ring holds ceil(n / 64) waves: it wraps too, which is how the export has always run).  Returns n."""
+    import os
+    from helpers import BIMERA_PAIR_OPTIONS, bimera_pair_cases
+    qs, ps = bimera_pair_cases(21, n, L)
+    lane_bits = sum(bit_nw(w, f) for w in NW_CLASSES for f in ("plain", "nonplain", "pair")) | bit_gen(False) | bit_gen(True)
+    old = os.environ.get("DADA2HIP_NW_KERNEL")
+    os.environ["DADA2HIP_NW_KERNEL"] = "lane"
+    try:
+        for oo, ms, sc in BIMERA_PAIR_OPTIONS:
+            want = oracle.bimera_pairs(qs, ps, oo, *sc, ms)
+            with ring(RING_WAVES):
+                read_ledger()
+                got = api.bimera_pairs(qs, ps, oo, *sc, ms)
+                ran = read_ledger() & ~GAPLESS_BITS
+                trips = read_ring_trips()
+            bad = np.nonzero((got != want).any(axis=1))[0]
+            assert bad.size == 0, (oo, ms, sc, describe(ran), [(int(i), qs[i], ps[i], got[i].tolist(), want[i].tolist()) for i in bad[:3]])
+            assert ran and not ran & ~lane_bits, describe(ran)
+            assert trips == -(-n // RING_WAVES) >= 3, (trips, "trips: DADA2HIP_NW_RING ignored?")
+            with ring(None):
+                plain = api.bimera_pairs(qs, ps, oo, *sc, ms)
+                assert read_ring_trips() < trips
+            assert np.array_equal(plain, got), (oo, ms, sc, "the ring's size changed a row")
+        # ... and the table form, where a query's parents FILL its chunks (64 lanes live, the query read through chunk_centre)
+        mat, seqs = ring_bimera_table()
+        for oo, ms in ((False, 16), (True, 8)):
+            want = oracle.table_bimera2(mat, seqs, min_fold=1.5, min_abund=2, allow_one_off=oo, max_shift=ms)
+            assert 0 < int((want[0] > 0).sum()) < len(seqs)
+            with ring(RING_WAVES):
+                read_ledger()
+                got = api.table_bimera2(mat, seqs, min_fold=1.5, min_abund=2, allow_one_off=oo, max_shift=ms)
+                ran = read_ledger() & ~GAPLESS_BITS
+                trips = read_ring_trips()
+            assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), (oo, ms, np.flatnonzero(got[0] != want[0])[:5])
+            assert ran and not ran & ~lane_bits and trips >= 3, (describe(ran), trips)
+            with ring(None):
+                plain = api.table_bimera2(mat, seqs, min_fold=1.5, min_abund=2, allow_one_off=oo, max_shift=ms)
+            assert np.array_equal(plain[0], got[0]) and np.array_equal(plain[1], got[1])
+    finally:
+        if old is None:
+            os.environ.pop("DADA2HIP_NW_KERNEL", None)
+        else:
+            os.environ["DADA2HIP_NW_KERNEL"] = old
+    return n
+
+
+# the goldens a whole dada() run wraps the ring on: nine and more births (one chunk per birth pair on four waves: three trips)
+RING_WHOLE_PATH = ("sam1F_default", "synth3000_default", "sam1F_homogap", "samPB_band32")     # (the last: 1.5 kb reads, ragged)
+
+
+def run_ring_whole_path(api, oracle, name):
+    """dada_uniques on a golden case under DADA2HIP_NW_KERNEL=lane and a ring of four waves.  The two launches of the run's
+    finish are the only lane launches that write aligned VIEWS: the final alignments (a centre per chunk through chunk_centre,
+    view rows by unique) and the birth pairs (one chunk per birth, view_by_chunk = 1: row = chunk).  With nine births and more
+    the birth launch makes three trips and more on four waves and the final one at least as many (a chunk and more per partition), so a view row or a chunk's centre taken from the
+    wave's number instead of the chunk's lands in birth_subs, the transition table and the quality tables - all compared, with
+    everything else, against the reference's golden and the oracle.  Then the same run with the knob unset: identical."""
+    import os
+    from helpers import P_RTOL, assert_results_equal, case_inputs
+    d, err, pri, opts, exp, meta = case_inputs(name)
+    nb = meta["nclust"] - 1
+    assert -(-nb // RING_WAVES) >= 3 and len(d.seqs) > 64 * RING_WAVES, (name, nb, len(d.seqs))
+    lane_bits = sum(bit_nw(w, f) for w in NW_CLASSES for f in ("plain", "nonplain")) | bit_gen(False)
+    env = {"DADA2HIP_NW_KERNEL": "lane"}
+    if opts.normalised().HOMOPOLYMER_GAP_PENALTY != opts.normalised().GAP_PENALTY:
+        env["DADA2HIP_AD_HOMO"] = "0"                  # (homopolymer gaps on the lane kernels)
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        with ring(RING_WAVES):
+            read_ledger()
+            got = api.dada_uniques(d.seqs, d.abundances, pri, err, d.quals, opts)
+            ran = read_ledger() & ~GAPLESS_BITS
+            trips = read_ring_trips()
+        assert ran and not ran & ~lane_bits, (name, describe(ran))
+        assert trips >= 3, (name, "sized for", trips, "trips: DADA2HIP_NW_RING ignored?")
+        assert got.nclust == meta["nclust"] and len(got.birth_subs["pos"]) > 0
+        assert_results_equal(got, exp, p_rtol=P_RTOL, check_birth_from="priors" not in meta)
+        assert_results_equal(got, oracle.dada_uniques(d.seqs, d.abundances, pri, err, d.quals, opts), p_rtol=P_RTOL, check_birth_from="priors" not in meta)
+        with ring(None):
+            plain = api.dada_uniques(d.seqs, d.abundances, pri, err, d.quals, opts)
+        assert_results_equal(got, plain, exact_float=True)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    return trips
+
+
+def ring_bimera_table(seed=77, nseq=100, L=110, nsam=3):
+    """(mat [samples, sequences], seqs): fourteen variants of one ancestor and two-parent chimeras of them - exact, with a
+    substitution, 5' trimmed - with the variants abundant and the chimeras rare, so that a chimera has up to a hundred candidate
+    parents: its chunks of 64 are full."""
+    rng = np.random.default_rng(seed)
+    anc = _rnd(rng, L)
+    true = list(dict.fromkeys(_sub(rng, anc, rng.choice(L, size=int(rng.integers(4, 13)), replace=False))[: L - int(rng.integers(0, 6))] for _ in range(14)))
+    seqs = list(true)
+    while len(seqs) < nseq:
+        a, b = (int(x) for x in rng.choice(len(true), 2, replace=False))
+        cut = int(rng.integers(10, L - 20))
+        ch = true[a][:cut] + true[b][cut:]
+        kind = int(rng.integers(0, 3))
+        if kind == 1:
+            ch = _sub(rng, ch, [int(rng.integers(0, len(ch)))])
+        elif kind == 2:
+            ch = ch[int(rng.integers(1, 12)):]
+        if ch not in seqs:
+            seqs.append(ch)
+    mat = np.zeros((nsam, len(seqs)), dtype=np.int32)
+    nt = len(true)
+    mat[:, :nt] = rng.integers(50, 400, size=(nsam, nt))
+    mat[:, nt:] = np.sort(rng.integers(2, 40, size=(nsam, len(seqs) - nt)), axis=1)[:, ::-1]
+    return mat, seqs
 
 
 def gap_runs(oracle, b, ci, i):

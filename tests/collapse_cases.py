@@ -386,3 +386,26 @@ def emu_run():
     assert np.array_equal(api.nwhamming(qs, rs), g["ev_plain"][sel][:, 1] + g["ev_plain"][sel][:, 2])
     assert api.nwhamming(qs[0], rs[0]) == int(ev[0, 1] + ev[0, 2]) and api.nweval(qs[0], rs[0]).shape == (3,)
     return "ok pairs %d columns 60 -> %d aligned %d nweval %d" % (n, len(want[1]), st["pairs_aligned"], len(qs))
+
+
+def ring_run(api, checker):
+    """The low-complexity table (200 columns over {A, C}, min_overlap 4: the screen passes nearly every pair and the bound
+    settles few) in ONE batch under a scratch ring of four waves (DADA2HIP_NW_RING=4): the pairs left to the aligner go out in one
+    call of the pair-form lane kernel - more than 512, so its waves wrap their slots - and the table equals the restatement's;
+    with the knob unset the same `into` in one trip.  Returns the number of aligned pairs."""
+    import aligner_cases as A
+    mat, seqs = low_complexity_table()
+    exp = restate(mat, seqs, checker, min_overlap=4)
+    with A.ring(A.RING_WAVES):
+        got = device_collapse(api, mat, seqs, min_overlap=4)
+        trips = A.read_ring_trips()
+    assert_same_table(got, exp, "low complexity, ring of 4 waves")
+    st = got[2]
+    assert st["batches"] == 1 and A.RING_MIN_WORK <= st["pairs_aligned"] <= 65536, st
+    assert trips == -(-(-(-st["pairs_aligned"] // 64)) // A.RING_WAVES) >= 3, (trips, st["pairs_aligned"], "DADA2HIP_NW_RING ignored?")
+    with A.ring(None):
+        plain = device_collapse(api, mat, seqs, min_overlap=4)
+        assert A.read_ring_trips() == 1
+    assert_same_table(plain, exp, "low complexity")
+    assert np.array_equal(plain[2]["into"], st["into"]) and plain[2]["pairs_aligned"] == st["pairs_aligned"]
+    return st["pairs_aligned"]

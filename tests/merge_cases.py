@@ -258,3 +258,34 @@ def large_case():
         assert max(first[:13200]) >= 65536 and min(first[:13200]) == 0          # (the 13 200 doubled pairs come first)
     return dict(name="pairs_66000", seqsF=seqsF, seqsR=seqsR, fwd=fwd, rev=rev, n0F=rng.integers(1, 50, size=300).astype(np.int32),
                 n0R=rng.integers(1, 50, size=220).astype(np.int32), options=[dict(max_mismatch=1)], fact=fact)
+
+
+def ring_case():
+    """30 forward x 20 reverse sequences of 45-125 nt cut from three templates of 150 nt, every combination a read pair: 600
+    unique pairs in one device call, long pairs beside short ones - what the aligner's scratch ring wraps on when
+    DADA2HIP_NW_RING makes it four waves (ten chunks of 64 pairs, the last of 24)."""
+    rng = np.random.default_rng(600)
+    tpl = [_rnd(rng, 150) for _ in range(3)]
+    seqsF, seqsR = [], []
+    for i in range(30):
+        t = tpl[i % 3]
+        n = (45, 125, 80, 60, 110)[i % 5] - i % 4
+        a = int(rng.integers(0, 20))
+        seqsF.append(t[a: a + n] if i % 4 else _flip(t[a: a + n], int(rng.integers(0, n))))
+    for j in range(20):
+        t = tpl[j % 3]
+        n = (120, 50, 95, 70)[j % 4] - j % 3
+        a = int(rng.integers(150 - n - 20, 150 - n + 1))
+        seqsR.append(rc(t[a: a + n]))
+    fwd = np.repeat(np.arange(1, 31, dtype=np.int32), 20)
+    rev = np.tile(np.arange(1, 21, dtype=np.int32), 30)
+    again = np.arange(0, fwd.size, 5)
+    fwd, rev = np.concatenate([fwd, fwd[again]]), np.concatenate([rev, rev[again]])
+
+    def fact(rows):
+        for rr in rows.values():
+            assert len(rr) == 600
+            assert sum(r["accept"] for r in rr) >= 40 and sum(not r["accept"] for r in rr) >= 300, sum(r["accept"] for r in rr)
+        assert any(r["accept"] and r["nmismatch"] == 1 for r in rows[1])
+    return dict(name="pairs_600_ring", seqsF=seqsF, seqsR=seqsR, fwd=fwd, rev=rev, n0F=rng.integers(1, 50, size=30).astype(np.int32),
+                n0R=rng.integers(1, 50, size=20).astype(np.int32), options=[dict(), dict(max_mismatch=1)], fact=fact)

@@ -368,6 +368,141 @@ def run_vec_case(api, oracle, case, ref=None, nalone=8):
     return ran
 
 
+# ---- the scratch ring's wrap: a wave's second and third chunk in the slot it has used ---------------------------------------------
+# launch_nw caps its waves at the ring ensure_scratch sized (4 096 waves, fewer for long unbanded reads), and a wave that gets a
+# second chunk of 64 pairs finds the first one's pointer rows, t-codes and DP row in its slot.  DADA2HIP_NW_RING=4 makes that
+# happen on 600 pairs: ten chunks on four waves, two waves with a third trip, the last chunk of 24 pairs.  The pair classes cycle
+# as in every batch (13 kinds against chunks of 64), so a lane of a reused slot goes from a long pair to a short one and back.
+RING_N = 600
+_RING_GEOMETRY = [GEOMETRY[0], GEOMETRY[2], GEOMETRY[4]] + SMALL_GEOMETRY + [GEOMETRY[10]]     # every pair instance at <= 130 nt; banded and unbanded k_nw_gen
+
+
+def ring_vec_cases():
+    """600 pairs per pair instance, ends free and global, plus the two-plane letters batch: the cases of the ring's wrap."""
+    out = []
+    for k, (name, band, lo, hi, bit) in enumerate(_RING_GEOMETRY):
+        for ef in (True, False):
+            sc = ("default", "flat", "merge")[(k + ef) % 3]
+            out.append(_vec("ring_%s_n%d_%s_ef%d" % (name, RING_N, sc, ef), band, lo, hi, RING_N, sc, ef, bit))
+    out.append(_vec("ring_letters_n%d_default_ef1" % RING_N, 16, 40, 60, RING_N, "default", True, bit_gen(True), letters=True))
+    names = [c.name for c in out]
+    assert len(set(names)) == len(names)
+    return out
+
+
+def run_ring_vec_case(api, oracle, case, ref=None):
+    """dada2hip_nwvec on the whole batch under a ring of four waves: both strings of every pair against the oracle, the ledger
+    shows the case's pair instance, dada2hip_nw_ring_trips says the launch was sized for three trips (an ignored knob fails
+    here); then the same call with the knob unset - one trip, identical strings.  Returns the ledger of the call."""
+    from aligner_cases import RING_MIN_WORK, RING_WAVES, read_ring_trips, ring
+    assert case.n >= RING_MIN_WORK and case.n % 64
+    b = build(case)
+    sc = SCORES[case.score]
+    want = expected(oracle, case, ref)
+    check_facts(oracle, case, want)
+    kinds_by_lane = {(i % 64): set() for i in range(case.n)}
+    for i in range(case.n):
+        kinds_by_lane[i % 64].add(len(b.s1[i]) + len(b.s2[i]) > case.minlen + case.maxlen)
+    assert all(len(v) == 2 for v in kinds_by_lane.values()), (case.name, "a lane whose pairs are all long or all short")
+    with ring(RING_WAVES):
+        read_ledger()
+        got = api.nwvec(b.s1, b.s2, sc[0], sc[1], sc[2], case.band, case.endsfree)
+        ran = read_ledger() & ~GAPLESS_BITS
+        trips = read_ring_trips()
+    assert len(got) == case.n
+    for i in range(case.n):
+        check_alignment(case.name + ":" + b.kinds[i], i, b.s1[i], b.s2[i], got[i], want[i])
+    assert ran == case.expect, (case.name, "ran", describe(ran), "expected", describe(case.expect))
+    assert trips >= 3, (case.name, "the launch was sized for", trips, "trips: DADA2HIP_NW_RING ignored?")
+    with ring(None):
+        plain = api.nwvec(b.s1, b.s2, sc[0], sc[1], sc[2], case.band, case.endsfree)
+        assert read_ring_trips() == 1, case.name
+    assert [tuple(x) for x in plain] == [tuple(x) for x in got], (case.name, "the ring's size changed an alignment")
+    return ran
+
+
+# ---- the wrap at the ring's AUTOMATIC size: unbanded pairs of 1 400-1 500 nt --------------------------------------------------------
+# ensure_scratch halves the ring while its pointer scratch would pass 6 x 2^28 words: at 1 500 nt unbanded (W = 3 001, 188 pointer
+# words per row, 1 501 x 188 x 64 words per wave) that leaves 64 waves, so a call of more than 4 096 pairs wraps with no knob set.
+# 4 200 pairs: 66 chunks on 64 waves, waves 0 and 1 take a second one, the last chunk holds 40 pairs.  The oracle aligns the
+# 24 distinct pairs of the pool once each; item i is pool pair i mod 24, and 4 096 mod 24 = 16: the pair a lane finds in its slot
+# from the first trip is another one.
+LONG_N = 4200
+LONG_RING_ITEMS = 64 * 64          # alignments per trip of the automatic ring at this geometry
+LONG_POOL = 24
+
+
+def long_pool(seed=1500):
+    """[(s1, s2, kind)]: 24 pairs of 1 400-1 500 nt - identical, substitutions, insertions and deletions inside, one side a prefix
+    of the other, unrelated; either side the longer one.  Both extreme lengths occur (the batch's window is 2 x 1 500 + 1)."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for k in range(LONG_POOL):
+        L = (1500, 1400, 1450, 1473, 1500, 1427)[(k + k // 6) % 6]
+        c = _rnd(rng, L)
+        kind = ("identical", "subs", "indels", "prefix", "unrelated", "subs+indels")[k % 6]
+        if kind == "identical":
+            b = c
+        elif kind == "subs":
+            b = _sub(rng, c, rng.choice(L, size=3 + 4 * k, replace=False))
+        elif kind in ("indels", "subs+indels"):
+            s = list(c)
+            for _ in range(2 + k % 7):                       # deletions and insertions of 1-9 bases inside the read
+                p, m = int(rng.integers(30, len(s) - 40)), int(rng.integers(1, 10))
+                if len(s) - m >= 1400 and (len(s) + m > 1500 or rng.random() < 0.5):
+                    del s[p: p + m]
+                else:
+                    s[p:p] = list(_rnd(rng, m))
+            b = "".join(s)
+            if kind == "subs+indels":
+                b = _sub(rng, b, rng.choice(len(b), size=12, replace=False))
+        elif kind == "prefix":
+            c = c if L > 1400 else _rnd(rng, 1500)
+            b = c[:1400]
+        else:
+            b = _rnd(rng, (1400, 1500, 1461)[k % 3])
+        out.append((c, b, kind) if k % 2 else (b, c, kind))
+    lens = [len(s) for a, b, _ in out for s in (a, b)]
+    assert min(lens) == 1400 and max(lens) == 1500 and len({(a, b) for a, b, _ in out}) == LONG_POOL
+    assert {k for _, _, k in out} == {"identical", "subs", "indels", "prefix", "unrelated", "subs+indels"}
+    return out
+
+
+def long_batch():
+    """(s1, s2, pool index of every item): LONG_N items, items one trip of the automatic ring apart hold different pairs."""
+    pool = long_pool()
+    idx = np.arange(LONG_N) % LONG_POOL
+    assert (idx[LONG_RING_ITEMS:] != idx[:-LONG_RING_ITEMS]).all() and LONG_N > LONG_RING_ITEMS and LONG_N % 64
+    return [pool[k][0] for k in idx], [pool[k][1] for k in idx], idx
+
+
+def run_long_batch(api, oracle):
+    """dada2hip_nwvec, band -1, ends free, default scores, on the 4 200 pairs with NO knob set: every item's two strings
+    against the oracle's alignment of its pool pair, k_nw_gen<pair> by the ledger, and dada2hip_nw_ring_trips >= 2 - the
+    automatic ring was smaller than the call.  Returns (trips, seconds of the call)."""
+    import time
+    from aligner_cases import read_ring_trips, ring
+    pool = long_pool()
+    s1, s2, idx = long_batch()
+    want = [tuple(oracle.C_nwalign(a, b, 5, -4, -8, None, -1, True)) for a, b, _ in pool]
+    assert sum(interior_gaps(al)[0] or interior_gaps(al)[1] for al in want) >= 6
+    with ring(None):
+        read_ledger()
+        t0 = time.time()
+        got = api.nwvec(s1, s2, 5, -4, -8, -1, True)
+        dt = time.time() - t0
+        ran = read_ledger() & ~GAPLESS_BITS
+        trips = read_ring_trips()
+    assert len(got) == LONG_N
+    for i in range(LONG_N):
+        k = int(idx[i])
+        if tuple(got[i]) != want[k]:
+            check_alignment("long:%s" % pool[k][2], i, s1[i], s2[i], got[i], want[k])
+    assert ran == bit_gen(True), describe(ran)
+    assert trips >= 2, ("the launch was sized for", trips, "trip: the automatic ring holds the whole call")
+    return trips, dt
+
+
 # ---- dada2hip_nwalign with homopolymer gaps: one pair per call, the pair's own W on the class boundary ------------------------------
 def _homo_pair(rng, long_len, short_len, swap):
     """A homopolymer-rich string and a stretch of it with run lengths changed by one and with the boundary between two adjacent

@@ -131,6 +131,12 @@ REGIME_EMU_JOBS = [
     (REGIME_QUICK, {}), (REGIME_QUICK, {"DADA2HIP_V2_TAIL": "chain"}), (REGIME_QUICK, {"DADA2HIP_ENGINE": "classic"}),
     # ... and of 4 200 (past the 4 096 full records the device keeps: index list + rebuild on the host)
     ("tied_4200", {}), ("tied_5000", {}),
+    # the crowd's 2 200 uniques on the launch chains with k2_shuffle / k2_pupdate capped at one block each (nine visits per thread)
+    # and at 3 / 2 blocks with blocking waits; the unfiltered shuffle (DADA2HIP_V2_FILTER=0) on the chains and in the persistent tail
+    # (no stat shows the grids launched or sh_filter: an ignored knob would leave these rows green - tests/test_gpu_regimes.py, ENGINES)
+    ("crowd_small", {"DADA2HIP_V2_TAIL": "chain", "DADA2HIP_V2_GRID_SHUFFLE": "1", "DADA2HIP_V2_GRID_PUPDATE": "1"}),
+    ("crowd_small", {"DADA2HIP_V2_TAIL": "chain", "DADA2HIP_V2_GRID_SHUFFLE": "3", "DADA2HIP_V2_GRID_PUPDATE": "2", "DADA2HIP_WAIT": "block"}),
+    ("crowd_small", {"DADA2HIP_V2_TAIL": "chain", "DADA2HIP_V2_FILTER": "0"}), ("crowd_small", {"DADA2HIP_V2_FILTER": "0"}),
 ]
 
 
@@ -143,7 +149,8 @@ def test_emulated_regime_jobs_cover_the_cases_the_table_names():
 
 @pytest.mark.parametrize("cases,env", REGIME_EMU_JOBS,
                          ids=["crowd", "crowd-tail-grid3", "crowd-chains", "ties-and-deep", "ties-and-deep-chains", "ties-and-deep-classic-engine",
-                              "ties-4200", "ties-5000"])
+                              "ties-4200", "ties-5000", "crowd-chains-grid1", "crowd-chains-grid3-2-blocking-waits", "crowd-chains-unfiltered-shuffle",
+                              "crowd-tail-unfiltered-shuffle"])
 def test_emulated_regimes_match_the_oracle(emu_lib, cases, env):
     """tests/regime_runner.py on the emulated library: each case's facts hold on the oracle (the sample reaches its regime),
     then every output against the oracle; the stats name the engine that ran."""
@@ -159,7 +166,11 @@ def test_emulated_regimes_match_the_oracle(emu_lib, cases, env):
             continue
         _, name, js = line.split(" ", 2)
         st = json.loads(js)
-        persistent = not env and "permuted" not in name            # (input that is not abundance-sorted runs in plain mode)
+        # (what leaves the persistent tail, of the knobs this table uses: DADA2HIP_V2_TAIL=chain and DADA2HIP_ENGINE=classic; input
+        #  that is not abundance-sorted runs in plain mode.  A row that leaves it by another knob - DADA2HIP_NO_AUTOBIRTH,
+        #  DADA2HIP_NO_SPECULATION, DADA2HIP_V3_FAIL_ENTRY, another process holding the slot - has to be named here first)
+        assert not set(env) & {"DADA2HIP_NO_AUTOBIRTH", "DADA2HIP_NO_SPECULATION", "DADA2HIP_V3_FAIL_ENTRY"}, env
+        persistent = "DADA2HIP_V2_TAIL" not in env and "DADA2HIP_ENGINE" not in env and "permuted" not in name
         if env.get("DADA2HIP_V3_GRID"):
             assert st["tail_launches"] > 0 and st["tail_blocks"] == int(env["DADA2HIP_V3_GRID"]), (name, st)
         else:
@@ -192,11 +203,18 @@ def test_emulated_regimes_match_the_oracle(emu_lib, cases, env):
                                  {"DADA2HIP_V2_TAIL": "chain"}, {"DADA2HIP_V2_TAIL": "chain", "DADA2HIP_V2_ALIGN": "commit"},
                                  {"DADA2HIP_V2_TAIL": "chain", "DADA2HIP_V2_LITE": "0", "DADA2HIP_V2_NBUF": "1", "DADA2HIP_V2_MOV_INLINE": "8"},
                                  {"DADA2HIP_V2_TAIL": "chain", "DADA2HIP_V2_ALIGN": "commit", "DADA2HIP_V2_NBUF": "1", "DADA2HIP_V2_CHAIN": "1",
-                                  "DADA2HIP_NODE_CAP": "1"}],
+                                  "DADA2HIP_NODE_CAP": "1"},
+                                 # the chains with k2_shuffle / k2_pupdate capped at one block each and at 3 / 2 blocks (threads stride over
+                                 # the uniques, as they do past 524 288 / 262 144 of them), the latter with blocking waits
+                                 {"DADA2HIP_V2_TAIL": "chain", "DADA2HIP_V2_GRID_SHUFFLE": "1", "DADA2HIP_V2_GRID_PUPDATE": "1"},
+                                 {"DADA2HIP_V2_TAIL": "chain", "DADA2HIP_V2_GRID_SHUFFLE": "3", "DADA2HIP_V2_GRID_PUPDATE": "2", "DADA2HIP_WAIT": "block"},
+                                 # the unfiltered shuffle the filtered default must agree with, on the chains and in the persistent tail
+                                 {"DADA2HIP_V2_TAIL": "chain", "DADA2HIP_V2_FILTER": "0"}, {"DADA2HIP_V2_FILTER": "0", "DADA2HIP_V3_GRID": "2"}],
                          ids=["default", "classic-engine", "lane-kernel", "wide-kernel", "align-at-commit-grid2", "tail-grid3", "tail-grid5-pauses",
                               "tail-grid2-ring1-nbuf1-grow", "tail-serial-grid2", "tail-overlap-no-wait-grid3", "tail-evaluate-on-every-call-grid4",
                               "tail-evaluate-apart-grid3", "tail-attempts-and-plain-calls-mixed-grid3", "exact-screen-full-aligner-grid2", "tail-xcd-barrier-grid7", "tail-xcd-barrier-grid5-pauses-ring2", "chains", "chains-align-at-commit", "chains-nolite-nbuf1-biglists",
-                              "chains-commit-nbuf1-chain1-grow"])
+                              "chains-commit-nbuf1-chain1-grow", "chains-grid1", "chains-grid3-2-blocking-waits", "chains-unfiltered-shuffle",
+                              "tail-unfiltered-shuffle-grid2"])
 def test_emulated_kernels_reproduce_the_reference_goldens(emu_lib, env):
     out = run_cases(emu_lib, ("sam1F_default", "sam1R_default") if not env else ("sam1F_default",), env)   # (CPU suite budget: both only once)
     assert "ok sam1F_default 10 " in out
@@ -433,6 +451,86 @@ def test_emulated_pairwise_exports_two_plane_letters(emu_lib, oracle_ref):
     ) % (ROOT, os.path.join(ROOT, "tests"), emu_lib)
     out = _run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0 and "pairwise letters: ok 1" in out.stdout, out.stdout[-2000:] + out.stderr[-6000:]
+
+
+# ---- the lane aligners' scratch ring under DADA2HIP_NW_RING=4: a wave's second and third chunk in the slot it has used ----------------
+RING_CODE = (
+    "import sys\n"
+    "sys.path[:0] = [%r, %r]\n"
+    "from dada2_amd import _lib\n"
+    "_lib.LIB_PATH = %r\n"
+    "import aligner_cases as A\n"
+    "import pair_cases as P\n"
+    "from dada2_amd import api\n"
+    "from oracle import cport\n"
+)
+
+
+def test_emulated_pair_exports_wrap_the_scratch_ring(emu_lib):
+    """tests/pair_cases.py's ring cases (600 pairs per pair instance, ends free and global, reads of at most 130 nt) on the
+    emulated library: the emulated counterpart of test_nwvec_wraps_the_scratch_ring_per_pair_instance."""
+    code = RING_CODE % (ROOT, os.path.join(ROOT, "tests"), emu_lib) + (
+        "cases = [c for c in P.ring_vec_cases() if not c.letters]\n"
+        "seen = 0\n"
+        "for c in cases:\n"
+        "    seen |= P.run_ring_vec_case(api, cport, c)\n"
+        "missing = [P.describe(b)[0] for b in P.pair_instances() if not seen & b]\n"
+        "assert not missing, missing\n"
+        "assert len(cases) >= 2 * len(P.pair_instances())\n"
+        "print('pair ring: ok', len(cases))\n")
+    out = _run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0 and "pair ring: ok" in out.stdout, out.stdout[-2000:] + out.stderr[-6000:]
+
+
+def test_emulated_two_plane_letters_wrap_the_scratch_ring(emu_lib, oracle_ref):
+    """... and the two-plane letters batch of 600 pairs against the reference's own C_nwvec call on raw bytes."""
+    code = RING_CODE % (ROOT, os.path.join(ROOT, "tests"), emu_lib) + (
+        "from oracle import ref\n"
+        "cases = [c for c in P.ring_vec_cases() if c.letters]\n"
+        "for c in cases:\n"
+        "    assert P.run_ring_vec_case(api, cport, c, ref=ref) == P.bit_gen(True)\n"
+        "assert len(cases) >= 1\n"
+        "print('letters ring: ok', len(cases))\n")
+    out = _run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0 and "letters ring: ok" in out.stdout, out.stdout[-2000:] + out.stderr[-6000:]
+
+
+def test_emulated_lane_aligners_bimera_route_and_merge_wrap_the_scratch_ring(emu_lib):
+    """The lane cases of tests/aligner_cases.py at the emulator's lengths, grown past 512 uniques, through
+    dada2hip_sample_compare; api.bimera_pairs on the lane route (k_nw + k_bimera_lr, a chunk and a query per pair); and
+    dada2hip_merge_pairs on 600 unique pairs - each under a ring of four waves against the oracle and against the same call
+    with the knob unset: the emulated counterparts of test_lane_aligners_wrap_their_scratch_ring,
+    test_bimera_pairs_on_the_lane_route_wrap_the_scratch_ring and test_device_merge_wraps_the_aligner_scratch_ring."""
+    code = RING_CODE % (ROOT, os.path.join(ROOT, "tests"), emu_lib) + (
+        "cases = A.ring_cases(small_only=True)\n"
+        "seen = 0\n"
+        "for c in cases:\n"
+        "    npairs, got = A.run_ring_case(api, cport, c, lean=True)\n"
+        "    assert npairs > 2 * A.RING_MIN_WORK\n"
+        "    seen |= got\n"
+        "want = [A.bit_nw(w, f) for w in (33, 65, 129, 193) for f in ('plain', 'nonplain')] + [A.bit_gen()]\n"
+        "assert len(cases) >= len(want) and all(seen & b for b in want), A.describe(seen)\n"
+        "assert A.run_ring_bimera(api, cport) == 600\n"
+        "import test_merge as T\n"
+        "assert T.run_ring() == 600\n"
+        "print('lane ring: ok', len(cases))\n")
+    out = _run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0 and "lane ring: ok" in out.stdout, out.stdout[-2000:] + out.stderr[-6000:]
+
+
+def test_emulated_whole_runs_on_the_lane_kernels_wrap_the_scratch_ring(emu_lib):
+    """aligner_cases.run_ring_whole_path on the emulated library: dada_uniques on goldens of nine and more births under
+    DADA2HIP_NW_KERNEL=lane and a ring of four waves - the final alignments (chunk_centre, views by unique) and the birth pairs
+    (view_by_chunk: one chunk and one view row per birth) make three trips and more; birth_subs, the transition and quality tables
+    and everything else against the golden and the oracle: the emulated counterpart of
+    test_whole_path_on_the_lane_kernels_wraps_the_scratch_ring."""
+    code = RING_CODE % (ROOT, os.path.join(ROOT, "tests"), emu_lib) + (
+        "for name in A.RING_WHOLE_PATH:\n"
+        "    assert A.run_ring_whole_path(api, cport, name) >= 3\n"
+        "assert len(A.RING_WHOLE_PATH) >= 4\n"
+        "print('whole-path ring: ok')\n")
+    out = _run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0 and "whole-path ring: ok" in out.stdout, out.stdout[-2000:] + out.stderr[-6000:]
 
 
 def test_emulated_bimera_mode_instances(emu_lib):

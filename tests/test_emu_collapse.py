@@ -24,3 +24,20 @@ def test_emulated_collapse_pairs_whole_function_and_nweval(emu_lib):   # noqa: F
     ) % (ROOT, os.path.join(ROOT, "tests"), emu_lib)
     out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ), capture_output=True, text=True, timeout=900)
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout[-2000:] + out.stderr[-4000:]
+
+
+def test_emulated_collapse_wraps_the_aligner_scratch_ring(emu_lib):   # noqa: F811
+    """collapse_cases.ring_run: more than 512 pairs in one call of the pair-form lane aligner under DADA2HIP_NW_RING=4, the table
+    against the restatement over the plain-C oracle, and the knob changes nothing."""
+    code = (
+        "import sys\n"
+        "sys.path[:0] = [%r, %r]\n"
+        "from dada2_amd import _lib\n"
+        "_lib.LIB_PATH = %r\n"
+        "import collapse_cases as cc\n"
+        "from dada2_amd import api\n"
+        "from oracle import cport\n"
+        "print('ring: ok', cc.ring_run(api, cport))\n"
+    ) % (ROOT, os.path.join(ROOT, "tests"), emu_lib)
+    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ), capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0 and out.stdout.startswith("ring: ok "), out.stdout[-2000:] + out.stderr[-4000:]

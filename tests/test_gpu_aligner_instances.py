@@ -133,6 +133,32 @@ def test_bimera_mode_instances(api, oracle_c, max_shift, diff, bit_default, bit_
     _SEEN["tests"] += 1
 
 
+# ---- 4b. the lane aligners' scratch ring: a wave's second and third chunk in the slot it has used ------------------------------------
+RING_CASES = A.ring_cases()
+
+
+@pytest.mark.parametrize("case", RING_CASES, ids=[c.name for c in RING_CASES])
+def test_lane_aligners_wrap_their_scratch_ring(api, oracle_c, case):
+    """The lane case's sample grown past 512 uniques under DADA2HIP_NW_RING=4 (256 alignments per trip, the last chunk ragged):
+    every unique against each centre, pair by pair against the oracle as the sweep does, three trips by
+    dada2hip_nw_ring_trips, and bit for bit what the same compare gives with the knob unset.  What this covers is a reused slot's
+    stale contents and the index of a later trip's results: dada2hip_sample_compare has ONE centre per launch and passes neither
+    chunk_centre nor a view, so a per-chunk centre is not exercised here (the bimera test below and
+    test_whole_path_on_the_lane_kernels_wraps_the_scratch_ring of tests/test_gpu_parity.py do that)."""
+    npairs, got = A.run_ring_case(api, oracle_c, case)
+    assert npairs > 2 * A.RING_MIN_WORK and got == case.expect
+
+
+def test_bimera_pairs_on_the_lane_route_wrap_the_scratch_ring(api, oracle_c):
+    """k_nw + k_bimera_lr under DADA2HIP_NW_KERNEL=lane and a ring of four waves: 600 pairs, each a chunk of its own with its
+    own query (chunk_centre is read per chunk, a wave's 150 chunks land at their own slots), against the oracle as
+    test_bimera_pair_quantities_match_the_reference[lane] does, and equal to the call with the knob unset; then
+    api.table_bimera2 on a table whose chimeras have up to a hundred candidate parents (chunks of 64 live lanes that share the
+    query chunk_centre names) against the oracle's flags.  These launches keep move strings and pass NO view: view_by_chunk is
+    not reached here (k_bimera_lr reads the moves by work index) - tests/test_gpu_parity.py's ring test covers it."""
+    assert A.run_ring_bimera(api, oracle_c) == 600
+
+
 # ---- 5. completeness ----------------------------------------------------------------------------------------------------------------
 def expected_instances():
     """Every instance the build holds and the dispatcher can reach, written out."""

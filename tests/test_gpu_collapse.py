@@ -169,6 +169,12 @@ def test_more_pairs_than_one_aligner_call_takes(api, oracle_c):
     assert all(st["into"][pos[q]] == pos[r] for q, r in tr["joined"].items()) and len(exp[1]) == len(tr["kept"]) < 20
 
 
+def test_collapse_wraps_the_aligner_scratch_ring(api, checker):
+    """More than 512 pairs in one aligner call under DADA2HIP_NW_RING=4: the table equals the restatement's, the launch was
+    sized for three trips and more, and the knob changes nothing."""
+    assert cc.ring_run(api, checker) > 512
+
+
 # ---- nweval / nwhamming ---------------------------------------------------------------------------------------------------------------
 def _pair_case(name):
     import pair_cases as P

@@ -53,6 +53,29 @@ def test_nwalign_homopolymer_gaps_per_pair_instance(api, oracle_c, case):
     _SEEN["tests"] += 1
 
 
+RING_CASES = P.ring_vec_cases()
+
+
+@pytest.mark.parametrize("case", RING_CASES, ids=[c.name for c in RING_CASES])
+def test_nwvec_wraps_the_scratch_ring_per_pair_instance(api, oracle_c, case, request):
+    """600 pairs under DADA2HIP_NW_RING=4 (256 pairs per trip: every wave of the launch goes back to the slot it has used, two
+    of them twice, the last chunk ragged) against the oracle string by string, per pair instance, ends free and global, and
+    the two-plane letters batch against the reference's own C_nwvec; dada2hip_nw_ring_trips shows three trips, and the same call
+    with the knob unset gives the same strings in one."""
+    ref = request.getfixturevalue("oracle_ref") if case.letters else None
+    assert P.run_ring_vec_case(api, oracle_c, case, ref=ref) == case.expect
+
+
+def test_nwvec_wraps_the_automatic_ring_on_unbanded_pairs_of_1500_nt(api, oracle_c):
+    """No knob: 4 200 unbanded pairs of 1 400-1 500 nt (the full-length 16S sequence table).  ensure_scratch sizes the ring to 64
+    waves there (4.6 GB of pointers), so waves 0 and 1 align a second chunk over their first; every item against the oracle's
+    alignment of its pool pair (24 distinct pairs, items 4 096 apart differ), dada2hip_nw_ring_trips says 2.
+    Measured once on the MI355X: 2.4 s the call, 2.6 s the test (k_nw_gen<pair> on 64 waves, every DP row through global scratch)."""
+    trips, dt = P.run_long_batch(api, oracle_c)
+    print("nwvec, %d unbanded pairs of 1 400-1 500 nt: %d trips, %.2f s" % (P.LONG_N, trips, dt))
+    assert trips == 2
+
+
 def test_every_pair_instance_ran_on_this_gpu():
     """Reads what the tests above recorded - each of them asserted the instance it names before recording it.  It needs the
     module run as a whole, in file order: the message says how many of those tests ran."""

@@ -37,6 +37,22 @@ def test_whole_path_matches_reference_goldens(api, oracle_c, name, nw_kernel, mo
     assert_results_equal(got, want, p_rtol=P_RTOL, check_birth_from="priors" not in meta)
 
 
+def _ring_whole_path_cases():
+    import aligner_cases
+    return aligner_cases.RING_WHOLE_PATH
+
+
+@pytest.mark.parametrize("name", _ring_whole_path_cases())
+def test_whole_path_on_the_lane_kernels_wraps_the_scratch_ring(api, oracle_c, name):
+    """The golden run on the lane kernels with DADA2HIP_NW_RING=4.  The finish of a run is where the lane kernels write aligned
+    views: the final alignments (a centre per chunk, view rows by unique) and the birth pairs (view_by_chunk: one chunk, one view
+    row per birth) - with nine births and more both make three trips on four waves (dada2hip_nw_ring_trips).  birth_subs, the
+    transition table, the quality tables and all the rest against the reference's golden and the oracle, and bit for bit what
+    the run gives with the knob unset."""
+    import aligner_cases
+    assert aligner_cases.run_ring_whole_path(api, oracle_c, name) >= 3
+
+
 @pytest.mark.parametrize("fq,band", [("sam1F", 16), ("samPB", 32)])
 def test_compare_round_matches_reference(api, fq, band):
     """lambda / hamming / class of one b_compare round against the reference's sub_new + compute_lambda_ts."""

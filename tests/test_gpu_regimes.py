@@ -69,6 +69,22 @@ def _persistent(st):
 ENGINES = {
     "default": ({}, lambda n, st: _persistent(st) and st["tail_mirror"] == 1 and st["overlap_on"] == 1),
     "chains": ({"DADA2HIP_V2_TAIL": "chain"}, lambda n, st: st["tail_launches"] == 0 and st["batch_compares"] > 0),
+    # the block caps of k2_shuffle / k2_pupdate (2 048 / 1 024 blocks of 256 threads: a thread strides only past 524 288 / 262 144
+    # uniques) forced down: one block each - the 8 192 and more uniques of crowd_large are 32 and more visits per thread, under
+    # the 1 000 the 16-bit per-thread counts of the shuffle pass allow - and 3 / 2 blocks, an uneven stride, with blocking waits
+    # (ACCEPTED GAP: the stats carry neither the grids launched nor sh_filter, so the predicates of these four rows are the plain
+    #  chains / tail ones and an ignored DADA2HIP_V2_GRID_* or _FILTER would leave them green - unlike DADA2HIP_NW_RING, which has
+    #  its diagnostic.  That the rows bite is shown by the break experiments of DESIGN section 12 only: a sweep cut to its first
+    #  visit turns the capped rows red and no other.)
+    "chains-grid1": ({"DADA2HIP_V2_TAIL": "chain", "DADA2HIP_V2_GRID_SHUFFLE": "1", "DADA2HIP_V2_GRID_PUPDATE": "1"},
+                     lambda n, st: st["tail_launches"] == 0 and st["batch_compares"] > 0),
+    "chains-grid3-2-blocking-waits": ({"DADA2HIP_V2_TAIL": "chain", "DADA2HIP_V2_GRID_SHUFFLE": "3", "DADA2HIP_V2_GRID_PUPDATE": "2",
+                                       "DADA2HIP_WAIT": "block"}, lambda n, st: st["tail_launches"] == 0 and st["batch_compares"] > 0),
+    # the unfiltered shuffle (every later call of a round visits every unique) the filtered default must agree with: on the
+    # chains and in the persistent tail, which runs the same shuffle_body and reads Eng2::sh_filter too
+    "chains-unfiltered-shuffle": ({"DADA2HIP_V2_TAIL": "chain", "DADA2HIP_V2_FILTER": "0"},
+                                  lambda n, st: st["tail_launches"] == 0 and st["batch_compares"] > 0),
+    "tail-unfiltered-shuffle": ({"DADA2HIP_V2_FILTER": "0"}, lambda n, st: _persistent(st) and st["tail_mirror"] == 1),
     "classic-engine": ({"DADA2HIP_ENGINE": "classic"}, lambda n, st: st["tail_launches"] == 0 and st["batch_compares"] == 0),
     # (a crowd variant takes six neighbours along when it is born: with four movers inline every such round pauses)
     "mirror-checked-grid5-pauses": ({"DADA2HIP_V3_MIRROR": "2", "DADA2HIP_V3_GRID": "5", "DADA2HIP_V2_MOV_INLINE": "4"},

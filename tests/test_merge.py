@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from helpers import GOLDEN, case_inputs
-from merge_cases import OPTION_SETS, constructed_cases, large_case, make_case
+from merge_cases import OPTION_SETS, constructed_cases, large_case, make_case, ring_case
 from oracle import cport, merge as omerge
 
 KEYS = ("sequence", "abundance", "forward", "reverse", "nmatch", "nmismatch", "nindel", "prefer", "accept")
@@ -204,11 +204,38 @@ def run_constructed(c):
         assert ran == (A.bit_gen(True) if want[k] else 0), (c["name"], o, A.describe(ran))
 
 
+def run_ring():
+    """dada2hip_merge_pairs on the 600 unique pairs of merge_cases.ring_case under a scratch ring of four waves
+    (DADA2HIP_NW_RING=4): rows equal to the oracle's under both option sets, k_nw_gen<pair> by the ledger, three trips by
+    dada2hip_nw_ring_trips; the same call with the knob unset gives the same rows in one trip."""
+    import aligner_cases as A
+    if "ring" not in _LARGE:
+        _LARGE["ring"] = ring_case()
+    c = _LARGE["ring"]
+    assert len({(int(f), int(r)) for f, r in zip(c["fwd"], c["rev"])}) == 600 >= A.RING_MIN_WORK
+    want = oracle_rows(c)
+    for k, o in enumerate(c["options"]):
+        with A.ring(A.RING_WAVES):
+            A.read_ledger()
+            rc_, msg, rows = _call_merge(c, **o)
+            ran = A.read_ledger() & ~A.GAPLESS_BITS
+            trips = A.read_ring_trips()
+        assert rc_ == 0, msg
+        assert_rows_equal(rows, want[k])
+        assert ran == A.bit_gen(True), A.describe(ran)
+        assert trips == 3, (trips, "trips: DADA2HIP_NW_RING ignored?")
+        with A.ring(None):
+            rc_, msg, plain = _call_merge(c, **o)
+            assert rc_ == 0 and A.read_ring_trips() == 1, msg
+        assert plain == rows, "the ring's size changed a row"
+    return len(want[0])
+
+
 def test_constructed_cases_reach_their_regimes():
     """Each constructed case's fact, from the oracle's rows: the overlap IS min_overlap and one less, the differences ARE
     max_mismatch and one more, trimming changes the sequence, prefer changes the sequence, ... - and the large case has more
     unique pairs than one device call takes, with accepted rows on both sides of the boundary."""
-    for c in CONSTRUCTED + [_the_large_case()]:
+    for c in CONSTRUCTED + [_the_large_case(), ring_case()]:
         oracle_rows(c)
 
 
@@ -246,3 +273,8 @@ def test_device_merge_across_the_65536_pair_chunk():
     P = len({(int(f), int(r)) for f, r in zip(c["fwd"], c["rev"])})
     assert P > 65536
     run_constructed(c)
+
+
+@pytest.mark.gpu
+def test_device_merge_wraps_the_aligner_scratch_ring():
+    assert run_ring() == 600
