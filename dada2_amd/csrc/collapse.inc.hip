@@ -1,4 +1,5 @@
-// collapse.inc.hip — the device side of collapseNoMismatch (R/multiSample.R:104-160); included by kernels.hip, inside namespace d2.
+// collapse.inc.hip — the device side of collapseNoMismatch (R/multiSample.R:104-160); included by kernels.hip, inside namespace d2,
+// behind seqkeys.inc.hip (bases16, the window key and the search of a key group).
 //
 // The reference walks, for every column of a sequence table, the columns it has kept so far; each step is two grepl() calls
 // (does the first minOverlap bases of one sequence occur in the other?) and, where either says yes, an unbanded ends-free
@@ -16,15 +17,6 @@
 
 constexpr int CL_MAXW = (SEQLEN + 15) / 16;   // 2-bit words of the longest row a resident sample takes (reads < SEQLEN)
 
-// sixteen bases (bits 2k..2k+1 = base b + k) of a packed row of nw words, from base b on; b may be negative or past the row:
-// bases outside [0, 16 nw) read as zero
-__device__ __forceinline__ uint32_t cl_bases16(const uint32_t *row, int nw, int b) {
-  const int w = b >> 4, sh = (b & 15) * 2;
-  const uint32_t lo = (w >= 0 && w < nw) ? row[w] : 0u;
-  const uint32_t hi = (w + 1 >= 0 && w + 1 < nw) ? row[w + 1] : 0u;
-  return (uint32_t)(((((uint64_t)hi) << 32) | lo) >> sh);
-}
-
 // One wave per sequence, a lane per window position; rows [row0, row0 + nrows) of the sample, bits[row - row0][KW] preset to 0.
 // keys: the distinct (length, first bases) prefix keys, ascending inside each length's group; groups[g] = {length, first key,
 // number of keys}.  A window that equals key k sets bit k of its sequence's row.
@@ -38,14 +30,10 @@ __global__ __launch_bounds__(256) void k_collapse_join(SampleDev S, int row0, in
     const uint32_t *row = S.seq2 + (size_t)sq * S.W2;
     for (int g = 0; g < ngroups; g++) {
       const int kl = groups[3 * g], first = groups[3 * g + 1], cnt = groups[3 * g + 2];
-      const unsigned long long mask = kl >= 32 ? ~0ull : ((1ull << (2 * kl)) - 1ull);
+      const unsigned long long mask = key_mask(kl);
       for (int p = lane; p + kl <= L; p += 64) {
-        const unsigned long long w = ((((unsigned long long)cl_bases16(row, nw, p + 16)) << 32) | cl_bases16(row, nw, p)) & mask;
-        int lo = first, hi = first + cnt;                 // the first key >= w of the group
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (keys[mid] < w) lo = mid + 1; else hi = mid;
-        }
+        const unsigned long long w = window_key(row, nw, p, mask);
+        const int lo = key_lower_bound(keys, first, cnt, w);
         if (lo < first + cnt && keys[lo] == w) atomicOr(&bits[(size_t)rr * KW + (lo >> 5)], 1u << (lo & 31));
       }
     }
@@ -86,7 +74,7 @@ __global__ __launch_bounds__(64) void k_collapse_scan(SampleDev S, const int2 *_
       const int i0 = max(0, s), i1 = min(lq, lr + s);
       int mm = 0, lead = -1;                               // lead: matching columns before the overlap's first mismatch
       for (int w = i0 >> 4; w <= (i1 - 1) >> 4; w++) {
-        const uint32_t x = s_q[w] ^ cl_bases16(s_r, wr, 16 * w - s);
+        const uint32_t x = s_q[w] ^ bases16(s_r, wr, 16 * w - s);
         const int lo = max(i0 - 16 * w, 0), hi = min(i1 - 16 * w, 16);   // the word's bases [lo, hi) lie in the overlap
         const uint32_t keep = (hi >= 16 ? ~0u : ((1u << (2 * hi)) - 1u)) & ~((1u << (2 * lo)) - 1u);
         const uint32_t f = (x | (x >> 1)) & 0x55555555u & keep;          // one bit per mismatching base

@@ -7,6 +7,7 @@
 // (k_collapse_join: which pairs can pass the screen at all; k_collapse_scan: the screen itself and the bound that settles most
 // pairs without a DP; the pair-form lane aligner for the rest, collapse.inc.hip), and the host replays the reference's choice
 // from the bulk results: each query joins the FIRST kept column, in kept order, whose pair holds.
+// From stage_common.h: require_acgt, the prefix keys and their groups (build_prefix_keys), the clocks and the end of a call.
 #pragma once
 #include <string_view>
 #include <unordered_map>
@@ -14,15 +15,6 @@
 #include "evalpair.h"
 
 namespace {
-
-void require_acgt(int n, const char *const *seqs, const char *what) {
-  for (int i = 0; i < n; i++) {
-    if (!seqs[i]) throw InputError{"dada2hip: bad arguments"};
-    for (const char *c = seqs[i]; *c; c++)
-      if (*c != 'A' && *c != 'C' && *c != 'G' && *c != 'T')
-        throw RuntimeErr{DADA2HIP_ERR_UNSUPPORTED, std::string("dada2hip: ") + what + " on the device takes A/C/G/T only."};
-  }
-}
 
 // match / mismatch / indel of C_eval_pair on the alignment of every pair; calls of at most 65 536 pairs, as merge.cpp's
 void nweval_pairs(size_t n, const char *const *s1, const char *const *s2, int match, int mismatch, int gap_p, int homo_gap_p, int band,
@@ -65,22 +57,15 @@ void collapse_scan_pairs(dada2hip_sample *s, const std::vector<int2> &pairs, int
     D2_HIP(hipMemcpyAsync(d_pairs.p, pairs.data() + p0, m * sizeof(int2), hipMemcpyHostToDevice, s->stream));
     launch_collapse_scan(s->D, d_pairs.p, (int)m, min_overlap, match, mismatch, use_bound ? 1 : 0, d_out.p, s->stream);
     D2_HIP(hipMemcpyAsync(out.data() + p0, d_out.p, m * sizeof(int4), hipMemcpyDeviceToHost, s->stream));
-    D2_HIP(hipStreamSynchronize(s->stream));
-    D2_HIP(hipGetLastError());
+    sync_checked(s->stream);
   }
 }
-
-enum { CS_NDEDUP = 0, CS_CAND, CS_SCANNED, CS_SCREENED_OUT, CS_BOUND, CS_ALIGNED, CS_HAM0, CS_BATCHES, CS_US_JOIN, CS_US_SCAN, CS_US_ALIGN,
-       CS_US_RESOLVE, CS_US_TOTAL };
 
 void collapse_body(int32_t nrow, int32_t ncol, const int32_t *mat, const char *const *seqs, int32_t min_overlap, int32_t identical_only,
                    int32_t band, int32_t match, int32_t mismatch, int32_t gap_p, int32_t device, int32_t *into, int64_t *stats) {
   auto t_call = clk::now();
   int64_t st[DADA2HIP_COLLAPSE_NSTATS] = {0};
-  auto finish = [&] {
-    st[CS_US_TOTAL] = (int64_t)(ms_since(t_call) * 1e3);
-    if (stats) memcpy(stats, st, sizeof st);
-  };
+  auto finish = [&] { finish_stats(st, CS_US_TOTAL, t_call, stats); };
   if (nrow < 0 || ncol < 0 || (ncol > 0 && (!seqs || !into || (nrow > 0 && !mat)))) throw InputError{"dada2hip: bad sequence table"};
   if (min_overlap < 1) throw InputError{"dada2hip: minOverlap must be at least 1."};
   if (ncol == 0) { finish(); return; }
@@ -139,41 +124,21 @@ void collapse_body(int32_t nrow, int32_t ncol, const int32_t *mat, const char *c
   // substr(q, 1, minOverlap) can occur in r only if key(q) does: (q, r) is a candidate iff key(q) occurs in r or key(r) in q.
   auto t0 = clk::now();
   std::vector<std::vector<int32_t>> keys_in, with_key, of_key;   // keys in sequence p; sequences with key k in them; with key k as theirs
-  std::vector<int32_t> key_of(nU);
+  PrefixKeyTable PK;
+  const std::vector<int32_t> &key_of = PK.key_of;
   if (use_join) {
-    struct Key { int32_t len; uint64_t w; };
-    std::vector<Key> kp(nU);
-    for (int p = 0; p < nU; p++) {
-      const int kl = std::min({(int)min_overlap, s->h_len[p], 32});
-      const uint32_t *row = s->h_seq2.p + (size_t)p * s->D.W2;
-      uint64_t w = row[0];
-      if (kl > 16) w |= (uint64_t)row[1] << 32;              // (W2 >= 4 words)
-      if (kl < 32) w &= ((uint64_t)1 << (2 * kl)) - 1;
-      kp[p] = Key{kl, w};
-    }
-    std::vector<Key> ks(kp);
-    auto less = [](const Key &a, const Key &b) { return a.len != b.len ? a.len < b.len : a.w < b.w; };
-    std::sort(ks.begin(), ks.end(), less);
-    ks.erase(std::unique(ks.begin(), ks.end(), [](const Key &a, const Key &b) { return a.len == b.len && a.w == b.w; }), ks.end());
-    const int nK = (int)ks.size(), KW = (nK + 31) / 32;
-    std::vector<unsigned long long> kw(nK);
-    std::vector<int32_t> groups;
-    for (int k = 0; k < nK; k++) {
-      kw[k] = ks[k].w;
-      if (k == 0 || ks[k].len != ks[k - 1].len) { groups.push_back(ks[k].len); groups.push_back(k); groups.push_back(0); }
-      groups.back()++;
-    }
+    std::vector<PrefixKey> kp(nU);
+    for (int p = 0; p < nU; p++) kp[p] = prefix_key(s->h_seq2.p + (size_t)p * s->D.W2, std::min({(int)min_overlap, s->h_len[p], 32}));
+    build_prefix_keys(kp, PK);
+    const int nK = (int)PK.keys.size(), KW = (nK + 31) / 32;
     of_key.resize(nK); with_key.resize(nK); keys_in.resize(nU);
-    for (int p = 0; p < nU; p++) {
-      key_of[p] = (int32_t)(std::lower_bound(ks.begin(), ks.end(), kp[p], less) - ks.begin());
-      of_key[key_of[p]].push_back(p);
-    }
+    for (int p = 0; p < nU; p++) of_key[key_of[p]].push_back(p);
     DevBuf<unsigned long long> d_keys;
     DevBuf<int32_t> d_groups;
     DevBuf<uint32_t> d_bits;
-    d_keys.alloc(nK); d_groups.alloc(groups.size());
-    D2_HIP(hipMemcpyAsync(d_keys.p, kw.data(), (size_t)nK * 8, hipMemcpyHostToDevice, s->stream));
-    D2_HIP(hipMemcpyAsync(d_groups.p, groups.data(), groups.size() * 4, hipMemcpyHostToDevice, s->stream));
+    d_keys.alloc(nK); d_groups.alloc(PK.groups.size());
+    D2_HIP(hipMemcpyAsync(d_keys.p, PK.keys.data(), (size_t)nK * 8, hipMemcpyHostToDevice, s->stream));
+    D2_HIP(hipMemcpyAsync(d_groups.p, PK.groups.data(), PK.groups.size() * 4, hipMemcpyHostToDevice, s->stream));
     // the bit matrix in blocks of rows of at most 256 MB
     const size_t rows_per = std::max<size_t>(1, ((size_t)256 << 20) / ((size_t)KW * 4));
     std::vector<uint32_t> h_bits;
@@ -181,10 +146,9 @@ void collapse_body(int32_t nrow, int32_t ncol, const int32_t *mat, const char *c
       const size_t nr = std::min(rows_per, (size_t)nU - r0);
       d_bits.alloc(nr * KW); h_bits.resize(nr * KW);
       D2_HIP(hipMemsetAsync(d_bits.p, 0, nr * KW * 4, s->stream));
-      launch_collapse_join(s->D, (int)r0, (int)nr, d_keys.p, d_groups.p, (int)groups.size() / 3, KW, d_bits.p, s->stream);
+      launch_collapse_join(s->D, (int)r0, (int)nr, d_keys.p, d_groups.p, (int)PK.groups.size() / 3, KW, d_bits.p, s->stream);
       D2_HIP(hipMemcpyAsync(h_bits.data(), d_bits.p, nr * KW * 4, hipMemcpyDeviceToHost, s->stream));
-      D2_HIP(hipStreamSynchronize(s->stream));
-      D2_HIP(hipGetLastError());
+      sync_checked(s->stream);
       for (size_t r = 0; r < nr; r++)
         for (int w = 0; w < KW; w++)
           for (uint32_t b = h_bits[r * KW + w]; b; b &= b - 1) {
@@ -194,7 +158,7 @@ void collapse_body(int32_t nrow, int32_t ncol, const int32_t *mat, const char *c
           }
     }
   }
-  st[CS_US_JOIN] = (int64_t)(ms_since(t0) * 1e3);
+  add_lap(st[CS_US_JOIN], t0);
 
   // ---- the greedy loop (:125-144), a batch of queries at a time ----
   enum : uint8_t { OPEN = 0, KEPT = 1, GONE = 2 };
@@ -225,7 +189,7 @@ void collapse_body(int32_t nrow, int32_t ncol, const int32_t *mat, const char *c
     st[CS_CAND] += (int64_t)pairs.size();
     t0 = clk::now();
     collapse_scan_pairs(s, pairs, min_overlap, match, mismatch, use_bound, scan);
-    st[CS_US_SCAN] += (int64_t)(ms_since(t0) * 1e3);
+    add_lap(st[CS_US_SCAN], t0);
     st[CS_SCANNED] += (int64_t)pairs.size();
     holds.assign(pairs.size(), 0);
     a1.clear(); a2.clear();
@@ -244,7 +208,7 @@ void collapse_body(int32_t nrow, int32_t ncol, const int32_t *mat, const char *c
         if (ev[3 * t + 1] + ev[3 * t + 2] == 0) { holds[where[t]] = 1; st[CS_HAM0]++; }
       st[CS_ALIGNED] += (int64_t)where.size();
     }
-    st[CS_US_ALIGN] += (int64_t)(ms_since(t0) * 1e3);
+    add_lap(st[CS_US_ALIGN], t0);
     t0 = clk::now();
     size_t i = 0;
     for (int q = b0; q < b1; q++) {            // the batch in order: a member that collapsed is no ref for the ones behind it
@@ -252,7 +216,7 @@ void collapse_body(int32_t nrow, int32_t ncol, const int32_t *mat, const char *c
       for (; i < pairs.size() && pairs[i].x == q; i++)
         if (state[q] == KEPT && holds[i] && state[pairs[i].y] == KEPT) { state[q] = GONE; joined[q] = pairs[i].y; }
     }
-    st[CS_US_RESOLVE] += (int64_t)(ms_since(t0) * 1e3);
+    add_lap(st[CS_US_RESOLVE], t0);
   }
   for (int p = 0; p < nU; p++) if (joined[p] >= 0) dest[ord[p]] = ord[joined[p]];
   // collapsed[, ref] + seqtab[, query] is integer arithmetic in the reference: NA past INT32_MAX

@@ -587,7 +587,12 @@ int dada2hip_sample_from_derep(const dada2hip_derep *d, const uint8_t *priors, i
 // qualities) and the offsets the kernels take; the kept records are laid out as ShortRead's writeFastq does (`@id`, the bases, a
 // bare `+`, the qualities) by the host pool and, with compress, deflated in pieces over the pool, every piece a gzip member of
 // its own (concatenated members are one valid .gz; a single deflate stream on one thread would be the whole run).
+#include "stage_stats.h"
+
 namespace {
+
+using fclk = std::chrono::steady_clock;
+inline int64_t us_since(fclk::time_point t) { return (int64_t)std::chrono::duration<double, std::micro>(fclk::now() - t).count(); }
 
 struct FqSource {
   std::string path;
@@ -685,9 +690,7 @@ struct FqWriter {
   // the read's reverse complement: its letters complemented and its qualities, both from the read's end backwards
   bool put(const FqChunk &c, const std::vector<uint8_t> &keep, const std::vector<int32_t> &win, const std::vector<uint8_t> &flip,
            std::string &err) {
-    using wclk = std::chrono::steady_clock;
-    auto us_since = [](wclk::time_point t) { return (int64_t)std::chrono::duration<double, std::micro>(wclk::now() - t).count(); };
-    auto t0 = wclk::now();
+    auto t0 = fclk::now();
     std::vector<size_t> at((size_t)c.n + 1, 0);
     for (int64_t i = 0; i < c.n; i++)
       at[i + 1] = at[i] + (keep[i] ? (size_t)(c.hoff[i + 1] - c.hoff[i]) + 2 * (size_t)win[2 * i + 1] + 5 : 0);
@@ -739,7 +742,7 @@ struct FqWriter {
       }
     });
     us_deflate += us_since(t0);
-    t0 = wclk::now();
+    t0 = fclk::now();
     for (size_t p = 0; p < np; p++) {
       if (zrc[p] != Z_OK) { err = "dada2hip: deflate failed while writing " + path; return false; }
       if (fwrite(z[p].data(), 1, z[p].size(), fp) != z[p].size()) { err = "dada2hip: error writing " + path; return false; }
@@ -753,6 +756,21 @@ struct FqWriter {
   }
 };
 
+// What the file-level entries share around fq_run_chunks (which settles the chunk size and re-reads the knobs): the constructor
+// starts the call's clock and resets the out-parameters, finish() sets the words every file has (reads in, reads out, the call's
+// total: stage_stats.h) and hands totals and counts to the caller.
+struct FqCall {
+  const fclk::time_point t_call = fclk::now();
+  int64_t *reads_in, *reads_out, nin = 0, nout = 0;
+  FqCall(int64_t *ri, int64_t *ro) : reads_in(ri), reads_out(ro) { if (ri) *ri = 0; if (ro) *ro = 0; }
+  int finish(int64_t *tot, size_t tot_bytes, int w_total, int64_t *stats) const {
+    tot[FS_IN] = nin; tot[FS_KEPT] = nout; tot[w_total] = us_since(t_call);
+    if (reads_in) *reads_in = nin; if (reads_out) *reads_out = nout;
+    if (stats) memcpy(stats, tot, tot_bytes);
+    return DADA2HIP_OK;
+  }
+};
+
 // The chunk pipeline of a file-level call (filterAndTrim's and removePrimers'): the inputs are opened, existing outputs removed,
 // and chunk after chunk is parsed on a thread of its own under the verdicts and the writing of the chunk before.
 // verdict(ch, first_chunk, keep, win, flip) settles a chunk: keep[i] (set to 1 on entry), win[k] (offset and length per read of
@@ -761,9 +779,10 @@ struct FqWriter {
 struct FqClockWords { int parse, deflate, write, inflate; };
 template <typename Verdict>
 int fq_run_chunks(int nfile, const char *const *in, const char *const *out, int32_t compress, int64_t chunk_reads, int64_t *tot,
-                  const FqClockWords &W, int64_t &nin, int64_t &nout, Verdict &&verdict, char *errbuf, size_t errlen) {
-  using fclk = std::chrono::steady_clock;
-  auto us_since = [](fclk::time_point t) { return (int64_t)std::chrono::duration<double, std::micro>(fclk::now() - t).count(); };
+                  const FqClockWords &W, FqCall &call, Verdict &&verdict, char *errbuf, size_t errlen) {
+  int64_t &nin = call.nin, &nout = call.nout;
+  if (chunk_reads <= 0) chunk_reads = 100000;                   // filterAndTrim(n = 1e5)
+  d2::knobs_reload();
   FqSource src[2];
   FqWriter wr[2];
   FqChunk chunks[2][2];                                         // [slot][file]: the parser fills one slot while the other is filtered and written
@@ -775,7 +794,6 @@ int fq_run_chunks(int nfile, const char *const *in, const char *const *out, int3
     wr[k].path = out[k]; wr[k].compress = compress != 0;
   }
   for (int k = 0; k < nfile; k++) (void)remove(out[k]);         // :634-640 (writeFastq does not overwrite)
-  nin = 0; nout = 0;
   std::vector<int32_t> win[2];
   std::vector<uint8_t> keep, flip;
   int rc = DADA2HIP_OK;
@@ -822,20 +840,10 @@ int fq_run_chunks(int nfile, const char *const *in, const char *const *out, int3
   return rc;
 }
 
-// FS_* of filter_host.h: the words of a call's stats that add up over chunks, and the file level's own
-enum { FQ_US_PARSE = 21, FQ_US_DEFLATE = 22, FQ_US_WRITE = 23, FQ_US_TOTAL = 24, FQ_US_INFLATE = 25 };
-void fq_add_stats(int64_t *tot, const int64_t *st) {
-  for (int i = 0; i < DADA2HIP_FILTER_NSTATS; i++)
-    if (i == 13 || i == 14) tot[i] = st[i]; else if (i != FQ_US_TOTAL) tot[i] += st[i];
-}
-
 int filter_files_body(dada2hip_filter *ctx, int nfile, const char *const *in, const char *const *out,
                       const dada2hip_filter_params *const *params, int32_t compress, int64_t chunk_reads, int64_t *reads_in,
                       int64_t *reads_out, int64_t *stats, char *errbuf, size_t errlen) {
-  using fclk = std::chrono::steady_clock;
-  const auto t_call = fclk::now();
-  if (reads_in) *reads_in = 0;
-  if (reads_out) *reads_out = 0;
+  FqCall call(reads_in, reads_out);
   for (int k = 0; k < nfile; k++)
     if (!in[k] || !out[k] || !params[k]) { set_err(errbuf, errlen, "File paths must be provided in character format."); return DADA2HIP_ERR_INPUT; }
   for (int a = 0; a < nfile; a++) {                             // :627, :887
@@ -847,15 +855,11 @@ int filter_files_body(dada2hip_filter *ctx, int nfile, const char *const *in, co
     for (int b = 0; b < a; b++)
       if (strcmp(out[a], out[b]) == 0 || strcmp(in[a], in[b]) == 0) { set_err(errbuf, errlen, "The output and input file names must be different."); return DADA2HIP_ERR_INPUT; }
   }
-  if (chunk_reads <= 0) chunk_reads = 100000;                   // filterAndTrim(n = 1e5)
-  d2::knobs_reload();
   dada2hip_filter_params P[2];
   for (int k = 0; k < nfile; k++) P[k] = *params[k];
   int64_t tot[DADA2HIP_FILTER_NSTATS] = {0}, st[DADA2HIP_FILTER_NSTATS];
-  int64_t nin = 0, nout = 0;
   std::vector<int32_t> code[2];
-  const int rc = fq_run_chunks(nfile, in, out, compress, chunk_reads, tot, FqClockWords{FQ_US_PARSE, FQ_US_DEFLATE, FQ_US_WRITE, FQ_US_INFLATE},
-                               nin, nout,
+  const int rc = fq_run_chunks(nfile, in, out, compress, chunk_reads, tot, FqClockWords{FS_US_PARSE, FS_US_DEFLATE, FS_US_WRITE, FS_US_INFLATE}, call,
                                [&](FqChunk *ch, bool first, std::vector<uint8_t> &keep, std::vector<int32_t> *win, std::vector<uint8_t> &) -> int {
     const int64_t n = ch[0].n;
     for (int k = 0; k < nfile; k++) {
@@ -864,38 +868,27 @@ int filter_files_body(dada2hip_filter *ctx, int nfile, const char *const *in, co
       const int r = dada2hip_filter_reads(ctx, n, ch[k].seq.data(), ch[k].qual.data(), ch[k].off.data(), &P[k], code[k].data(), win[k].data(),
                                           nullptr, nullptr, nullptr, nullptr, st, errbuf, errlen);
       if (r != DADA2HIP_OK) return r;
-      if (k == 0) fq_add_stats(tot, st);
-      else for (int i = 15; i <= 20; i++) tot[i] += st[i];     // (the verdict counts are the forward reads'; the clocks are both files')
+      // (the verdict counts are the forward reads', the clocks both files'; stage_stats.h: which words add, are taken, are the file's)
+      const int w0 = k == 0 ? 0 : FS_CLOCK_FIRST, w1 = k == 0 ? FS_COUNT - 1 : FS_CLOCK_LAST;
+      for (int i = w0; i <= w1; i++)
+        if (i >= FS_TAKEN_FIRST && i <= FS_TAKEN_LAST) tot[i] = st[i]; else if (i != FS_US_TOTAL) tot[i] += st[i];
       for (int64_t i = 0; i < n; i++) if (code[k][i] != 0) keep[i] = 0;
     }
     return DADA2HIP_OK;
   }, errbuf, errlen);
-  if (rc != DADA2HIP_OK) return rc;
-  tot[0] = nin; tot[1] = nout;
-  tot[FQ_US_TOTAL] = (int64_t)std::chrono::duration<double, std::micro>(fclk::now() - t_call).count();
-  if (reads_in) *reads_in = nin;
-  if (reads_out) *reads_out = nout;
-  if (stats) memcpy(stats, tot, sizeof tot);
-  return DADA2HIP_OK;
+  return rc != DADA2HIP_OK ? rc : call.finish(tot, sizeof tot, FS_US_TOTAL, stats);
 }
 
 // removePrimers' file level (R/filter.R:116-225): dada2hip_primers_reads per chunk, the kept windows written in the kept
 // orientation, and the whole-file rule (:157-158) at the end - it asks for the matches of the reads AS GIVEN, summed over the file
-enum { PQ_HITS_FWD = 8, PQ_HITS_REV = 9, PQ_US_PARSE = 16, PQ_US_DEFLATE = 17, PQ_US_WRITE = 18, PQ_US_TOTAL = 19, PQ_US_INFLATE = 20 };
 int primers_file_body(const char *in, const char *out, const dada2hip_primer_params *params, int32_t compress, int64_t chunk_reads,
                       int32_t device, int64_t *reads_in, int64_t *reads_out, int64_t *stats, char *errbuf, size_t errlen) {
-  using fclk = std::chrono::steady_clock;
-  const auto t_call = fclk::now();
-  if (reads_in) *reads_in = 0;
-  if (reads_out) *reads_out = 0;
+  FqCall call(reads_in, reads_out);
   if (!in || !out || !params) { set_err(errbuf, errlen, "File paths must be provided in character format."); return DADA2HIP_ERR_INPUT; }
   if (strcmp(in, out) == 0) { set_err(errbuf, errlen, "Output files must be distinct from the input files."); return DADA2HIP_ERR_INPUT; }   // :102
-  if (chunk_reads <= 0) chunk_reads = 100000;
-  d2::knobs_reload();
   int64_t tot[DADA2HIP_PRIMERS_NSTATS] = {0}, st[DADA2HIP_PRIMERS_NSTATS];
-  int64_t nin = 0, nout = 0;
   std::vector<int32_t> code, flip32, first, last;
-  int rc = fq_run_chunks(1, &in, &out, compress, chunk_reads, tot, FqClockWords{PQ_US_PARSE, PQ_US_DEFLATE, PQ_US_WRITE, PQ_US_INFLATE}, nin, nout,
+  int rc = fq_run_chunks(1, &in, &out, compress, chunk_reads, tot, FqClockWords{PS_US_PARSE, PS_US_DEFLATE, PS_US_WRITE, PS_US_INFLATE}, call,
                          [&](FqChunk *ch, bool, std::vector<uint8_t> &keep, std::vector<int32_t> *win, std::vector<uint8_t> &flip) -> int {
     const int64_t n = ch[0].n;
     code.resize((size_t)n); flip32.resize((size_t)n); first.resize((size_t)n); last.resize((size_t)n);
@@ -907,14 +900,14 @@ int primers_file_body(const char *in, const char *out, const dada2hip_primer_par
         for (int64_t i = 0; i < n; i++)
           if (code[i] == 4) {
             const std::string id(ch[0].hdr.data() + ch[0].hoff[i], (size_t)(ch[0].hoff[i + 1] - ch[0].hoff[i]));
-            set_err(errbuf, errlen, ("dada2hip: read " + std::to_string(nin - n + i + 1) + " (" + id +
+            set_err(errbuf, errlen, ("dada2hip: read " + std::to_string(call.nin - n + i + 1) + " (" + id +
                                      ") holds a letter outside the upper-case IUPAC codes ACGTMRWSYKVHDBN.").c_str());
             break;
           }
       }
       return r;
     }
-    for (int i = 0; i < PQ_US_PARSE; i++) tot[i] += st[i];
+    for (int i = 0; i <= PS_CALL_LAST; i++) tot[i] += st[i];
     for (int64_t i = 0; i < n; i++) {
       if (code[i] != 0) { keep[i] = 0; continue; }
       win[0][2 * i] = first[i] - 1; win[0][2 * i + 1] = last[i] - first[i] + 1;   // :213 narrow(fq, first, last)
@@ -923,16 +916,11 @@ int primers_file_body(const char *in, const char *out, const dada2hip_primer_par
     return DADA2HIP_OK;
   }, errbuf, errlen);
   if (rc != DADA2HIP_OK) return rc;
-  if (tot[PQ_HITS_FWD] == 0 || (params->primer_rev && tot[PQ_HITS_REV] == 0)) {   // :157-158
+  if (tot[PS_HITS_FWD] == 0 || (params->primer_rev && tot[PS_HITS_REV] == 0)) {   // :157-158
     (void)remove(out);
-    nout = 0;
+    call.nout = 0;
   }
-  tot[0] = nin; tot[1] = nout;
-  tot[PQ_US_TOTAL] = (int64_t)std::chrono::duration<double, std::micro>(fclk::now() - t_call).count();
-  if (reads_in) *reads_in = nin;
-  if (reads_out) *reads_out = nout;
-  if (stats) memcpy(stats, tot, sizeof tot);
-  return DADA2HIP_OK;
+  return call.finish(tot, sizeof tot, PS_US_TOTAL, stats);
 }
 
 template <typename F> int filter_files_guarded(char *errbuf, size_t errlen, F &&f) {

@@ -3564,6 +3564,12 @@ int dada2hip_nwalign(const char *s1, const char *s2, int32_t match, int32_t mism
   return nwvec_any(1, a, b, match, mismatch, gap_p, homo_gap_p, band, endsfree, device, o, errbuf, errlen);
 }
 
+// ---- what the five stages below share: stats words, small helpers, prefix keys; the two-slot read pipeline ----
+extern "C++" {
+#include "stage_common.h"
+#include "read_pieces.h"
+}
+
 // ---- the sequence-table stage: collapseNoMismatch, nweval (R/multiSample.R:104-160, R/misc.R:216-225) ----
 #include "collapse_host.h"
 

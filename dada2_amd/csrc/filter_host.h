@@ -6,38 +6,11 @@
 // word_size letters, its `len` windows) for the reference and for its reverse complement (R/filter.R:1183) as ONE sorted array of
 // distinct keys with two flag bits, in the key form of filter.inc.hip, and the two tables pow(10.0, -q / 10.0) per quality
 // CHARACTER (offset 33 and 64) with the host's pow, so that every term of the EE sum is the reference's bit for bit.
-// dada2hip_filter_reads cuts the call into pieces of at most FT_PIECE_READS reads / FT_PIECE_BYTES bytes (DADA2HIP_FILTER_PIECE,
-// DADA2HIP_FILTER_PIECE_BYTES: fewer, for the tests) and runs them through two slots, each with pinned staging, device buffers and
-// a stream of its own: while the kernels of one piece run, the host copies the next piece into the other slot's pinned buffers and
-// queues its upload, so the copy of piece k + 1 runs under the kernels of piece k.  The Shannon number of seqComplexity
-// (:1271-1275) is computed here from the device's integer counts.
+// dada2hip_filter_reads takes sequences and qualities up through read_pieces.h's two-slot pipeline (DADA2HIP_FILTER_PIECE,
+// DADA2HIP_FILTER_PIECE_BYTES: smaller pieces, for the tests), the slots kept in the context, and supplies the three kernels
+// between four events and the scatter, where the Shannon number of seqComplexity (:1271-1275) is computed from the device's
+// integer counts.  From stage_common.h: the A/C/G/T code, the reverse complement, the clocks, the end of a call.
 #pragma once
-
-namespace {
-
-constexpr int64_t FT_PIECE_READS = 1 << 16;
-constexpr int64_t FT_PIECE_BYTES = 32 << 20;
-
-struct FtSlot {
-  PinBuf<uint8_t> h_seq, h_qual;
-  PinBuf<long long> h_off;
-  PinBuf<FilterOut> h_out;
-  PinBuf<int32_t> h_km;
-  DevBuf<uint8_t> d_seq, d_qual;
-  DevBuf<long long> d_off;
-  DevBuf<FilterOut> d_out;
-  DevBuf<int32_t> d_km;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  int64_t first = 0, count = 0;
-  bool busy = false;
-  ~FtSlot() {
-    for (int i = 0; i < 4; i++) if (ev[i]) (void)hipEventDestroy(ev[i]);
-    if (st) (void)hipStreamDestroy(st);
-  }
-};
-
-}  // namespace
 
 struct dada2hip_filter {
   int device = 0;
@@ -46,16 +19,13 @@ struct dada2hip_filter {
   DevBuf<unsigned long long> keys;
   DevBuf<uint8_t> flags;
   DevBuf<double> ee_tab;               // [2][256]: offset 33, offset 64
-  FtSlot slot[2];
+  PieceSlot<FilterOut, 4> slot[2];     // aux: the k-mer counts
   std::mutex mu;                       // calls on one context take turns (its slots and streams)
 };
 
 namespace {
 
-enum { FS_IN = 0, FS_KEPT, FS_STAGE1, FS_KEYS = 13, FS_LDS, FS_BYTES, FS_US_UP, FS_US_SCAN, FS_US_EE, FS_US_KMERS, FS_US_DOWN, FS_US_PARSE,
-       FS_US_DEFLATE, FS_US_WRITE, FS_US_TOTAL };
-
-inline int ft_base(char c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }
+using FtSlot = PieceSlot<FilterOut, 4>;
 
 // the keys of the `len` circular windows of s (filter.inc.hip's form: the two bit planes of the window side by side)
 void ft_strand_keys(const std::string &s, int W, std::vector<unsigned long long> &keys) {
@@ -67,7 +37,7 @@ void ft_strand_keys(const std::string &s, int W, std::vector<unsigned long long>
     for (size_t i = lo; i < hi; i++) {
       unsigned long long k = 0;
       for (int t = 0; t < W; t++) {
-        const unsigned long long b = (unsigned long long)ft_base(e[i + (size_t)t]);
+        const unsigned long long b = (unsigned long long)acgt_code(e[i + (size_t)t]);
         k |= (b & 1ull) << t | (b >> 1) << (32 + t);
       }
       keys[i] = k;
@@ -85,14 +55,12 @@ void filter_open_body(const char *ref, int32_t word_size, int32_t device, dada2h
     if (word_size < 1 || word_size > 32) throw RuntimeErr{DADA2HIP_ERR_UNSUPPORTED, "dada2hip: the screen's word size must be 1..32 (one 64-bit key)."};
     const std::string s(ref);
     for (char c : s)
-      if (ft_base(c) < 0) throw RuntimeErr{DADA2HIP_ERR_UNSUPPORTED, "dada2hip: the screen's reference sequence must be upper-case A/C/G/T only."};
+      if (acgt_code(c) < 0) throw RuntimeErr{DADA2HIP_ERR_UNSUPPORTED, "dada2hip: the screen's reference sequence must be upper-case A/C/G/T only."};
     if (s.size() < (size_t)word_size) throw InputError{"dada2hip: the screen's reference sequence is shorter than the word size."};
     if (s.size() > (size_t)1 << 28) throw InputError{"dada2hip: the screen's reference sequence is too long."};
-    std::string rc(s.rbegin(), s.rend());
-    for (char &c : rc) c = "TGCA"[ft_base(c)];
     std::vector<unsigned long long> kf, kr;
     ft_strand_keys(s, word_size, kf);
-    ft_strand_keys(rc, word_size, kr);
+    ft_strand_keys(revcomp_acgt(s), word_size, kr);
     std::vector<std::pair<unsigned long long, uint8_t>> all;
     all.reserve(kf.size() + kr.size());
     for (unsigned long long k : kf) all.emplace_back(k, (uint8_t)1);
@@ -112,21 +80,16 @@ void filter_open_body(const char *ref, int32_t word_size, int32_t device, dada2h
   std::unique_ptr<dada2hip_filter> m(new dada2hip_filter());
   m->device = device; m->word_size = ref ? word_size : 0; m->nkeys = (int)keys.size();
   m->in_lds = !keys.empty() && keys.size() * 9 + 8 <= (size_t)FT_LDS_MAX;
-  for (FtSlot &S : m->slot) {
-    D2_HIP(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
-    for (int i = 0; i < 4; i++) D2_HIP(hipEventCreate(&S.ev[i]));
-  }
+  for (FtSlot &S : m->slot) S.create();
   m->keys.alloc(keys.size()); m->flags.alloc(flags.size()); m->ee_tab.alloc(512);
   if (!keys.empty()) {
     D2_HIP(hipMemcpy(m->keys.p, keys.data(), keys.size() * 8, hipMemcpyHostToDevice));
     D2_HIP(hipMemcpy(m->flags.p, flags.data(), flags.size(), hipMemcpyHostToDevice));
   }
   D2_HIP(hipMemcpy(m->ee_tab.p, tab.data(), 512 * 8, hipMemcpyHostToDevice));
-  if (stats) {
-    memset(stats, 0, DADA2HIP_FILTER_NSTATS * sizeof(int64_t));
-    stats[FS_KEYS] = m->nkeys; stats[FS_LDS] = m->in_lds ? 1 : 0; stats[FS_BYTES] = (int64_t)(keys.size() * 9 + 512 * 8);
-    stats[FS_US_TOTAL] = (int64_t)(ms_since(t_call) * 1e3);
-  }
+  int64_t st[DADA2HIP_FILTER_NSTATS] = {0};
+  st[FS_KEYS] = m->nkeys; st[FS_LDS] = m->in_lds ? 1 : 0; st[FS_BYTES] = (int64_t)(keys.size() * 9 + 512 * 8);
+  finish_stats(st, FS_US_TOTAL, t_call, stats);
   *out = m.release();
 }
 
@@ -173,19 +136,21 @@ void filter_reads_body(dada2hip_filter *m, int64_t n, const char *seq, const cha
   std::lock_guard<std::mutex> lock(m->mu);
   select_device(m->device);
   const double *d_tab = m->ee_tab.p + (offset == 64 ? 256 : 0);
-  auto harvest = [&](FtSlot &S) {
-    if (!S.busy) return;
-    auto t0 = clk::now();
-    D2_HIP(hipStreamSynchronize(S.st));
-    D2_HIP(hipGetLastError());
-    S.busy = false;
-    float ms = 0.0f;
-    D2_HIP(hipEventElapsedTime(&ms, S.ev[0], S.ev[1])); st[FS_US_SCAN] += (int64_t)((double)ms * 1e3);
-    D2_HIP(hipEventElapsedTime(&ms, S.ev[1], S.ev[2])); st[FS_US_EE] += (int64_t)((double)ms * 1e3);
-    D2_HIP(hipEventElapsedTime(&ms, S.ev[2], S.ev[3])); st[FS_US_KMERS] += (int64_t)((double)ms * 1e3);
+  // ---- the stage's part of the pipeline: three kernels between four events; the scatter ----
+  auto launch = [&](FtSlot &S, int c) {
+    launch_filter_scan(T, A, c, S.d_seq.p, S.d_qual.p, S.d_off.p, S.d_out.p, S.st);
+    D2_HIP(hipEventRecord(S.ev[1], S.st));
+    launch_filter_ee(A, c, S.d_qual.p, S.d_off.p, d_tab, S.d_out.p, S.st);
+    D2_HIP(hipEventRecord(S.ev[2], S.st));
+    if (want_km) launch_filter_kmers(c, k, S.d_seq.p, S.d_off.p, S.d_out.p, S.d_aux.p, S.st);
+  };
+  auto scatter = [&](FtSlot &S) {
+    add_elapsed(st[FS_US_SCAN], S.ev[0], S.ev[1]);
+    add_elapsed(st[FS_US_EE], S.ev[1], S.ev[2]);
+    add_elapsed(st[FS_US_KMERS], S.ev[2], S.ev[3]);
     const int64_t f = S.first, c = S.count;
     const FilterOut *o = S.h_out.p;
-    const int32_t *km = S.h_km.p;
+    const int32_t *km = S.h_aux.p;
     int64_t dropped[12] = {0};
     std::mutex cmu;
     parallel_for((size_t)c, 4096, [&](size_t lo, size_t hi) {
@@ -218,50 +183,10 @@ void filter_reads_body(dada2hip_filter *m, int64_t n, const char *seq, const cha
     });
     st[FS_KEPT] += dropped[0];
     for (int s = 1; s < 12; s++) st[FS_STAGE1 + s - 1] += dropped[s];
-    st[FS_US_DOWN] += (int64_t)(ms_since(t0) * 1e3);
   };
-  struct Drain { dada2hip_filter *m; ~Drain() { for (FtSlot &S : m->slot) if (S.busy) { (void)hipStreamSynchronize(S.st); S.busy = false; } } } drain{m};
-
-  const int64_t piece_reads = knobs().filter_piece > 0 ? std::min<int64_t>(knobs().filter_piece, FT_PIECE_READS) : FT_PIECE_READS;
-  const int64_t piece_bytes = knobs().filter_piece_bytes > 0 ? std::min<int64_t>(knobs().filter_piece_bytes, FT_PIECE_BYTES) : FT_PIECE_BYTES;
-  int64_t r0 = 0;
-  for (int piece = 0; r0 < n; piece++) {
-    int64_t r1 = r0 + 1;
-    while (r1 < n && r1 - r0 < piece_reads && offsets[r1 + 1] - offsets[r0] <= piece_bytes) r1++;
-    FtSlot &S = m->slot[piece & 1];
-    harvest(S);
-    auto t_up = clk::now();
-    const int64_t c = r1 - r0, base = offsets[r0], bytes = offsets[r1] - base;
-    S.h_seq.alloc((size_t)bytes); S.h_qual.alloc((size_t)bytes); S.h_off.alloc((size_t)c + 1); S.h_out.alloc((size_t)c);
-    S.d_seq.alloc((size_t)bytes); S.d_qual.alloc((size_t)bytes); S.d_off.alloc((size_t)c + 1); S.d_out.alloc((size_t)c);
-    if (want_km) { S.h_km.alloc((size_t)c * nb); S.d_km.alloc((size_t)c * nb); }
-    parallel_for((size_t)bytes, (size_t)1 << 20, [&](size_t lo, size_t hi) {
-      memcpy(S.h_seq.p + lo, seq + base + lo, hi - lo);
-      memcpy(S.h_qual.p + lo, qual + base + lo, hi - lo);
-    });
-    for (int64_t i = 0; i <= c; i++) S.h_off.p[i] = (long long)(offsets[r0 + i] - base);
-    if (bytes > 0) {
-      D2_HIP(hipMemcpyAsync(S.d_seq.p, S.h_seq.p, (size_t)bytes, hipMemcpyHostToDevice, S.st));
-      D2_HIP(hipMemcpyAsync(S.d_qual.p, S.h_qual.p, (size_t)bytes, hipMemcpyHostToDevice, S.st));
-    }
-    D2_HIP(hipMemcpyAsync(S.d_off.p, S.h_off.p, (size_t)(c + 1) * 8, hipMemcpyHostToDevice, S.st));
-    D2_HIP(hipEventRecord(S.ev[0], S.st));
-    launch_filter_scan(T, A, (int)c, S.d_seq.p, S.d_qual.p, S.d_off.p, S.d_out.p, S.st);
-    D2_HIP(hipEventRecord(S.ev[1], S.st));
-    launch_filter_ee(A, (int)c, S.d_qual.p, S.d_off.p, d_tab, S.d_out.p, S.st);
-    D2_HIP(hipEventRecord(S.ev[2], S.st));
-    if (want_km) launch_filter_kmers((int)c, k, S.d_seq.p, S.d_off.p, S.d_out.p, S.d_km.p, S.st);
-    D2_HIP(hipEventRecord(S.ev[3], S.st));
-    D2_HIP(hipMemcpyAsync(S.h_out.p, S.d_out.p, (size_t)c * sizeof(FilterOut), hipMemcpyDeviceToHost, S.st));
-    if (want_km) D2_HIP(hipMemcpyAsync(S.h_km.p, S.d_km.p, (size_t)c * nb * 4, hipMemcpyDeviceToHost, S.st));
-    S.first = r0; S.count = c; S.busy = true;
-    st[FS_BYTES] += 2 * bytes + (c + 1) * 8;
-    st[FS_US_UP] += (int64_t)(ms_since(t_up) * 1e3);
-    r0 = r1;
-  }
-  harvest(m->slot[0]); harvest(m->slot[1]);
-  st[FS_US_TOTAL] = (int64_t)(ms_since(t_call) * 1e3);
-  if (stats) memcpy(stats, st, sizeof st);
+  run_pieces(m->slot, n, seq, qual, offsets, knobs().filter_piece, knobs().filter_piece_bytes, want_km ? (size_t)nb : 0, st, FS_BYTES,
+             FS_US_UP, FS_US_DOWN, launch, scatter);
+  finish_stats(st, FS_US_TOTAL, t_call, stats);
 }
 
 }  // namespace

@@ -2901,6 +2901,7 @@ void launch_bimera_lr(const SampleDev &S, const int32_t *d_chunk_centre, const i
                      d_nmoves, allow_one_off, max_shift, d_out);
 }
 
+#include "seqkeys.inc.hip"    // packed 2-bit rows: sixteen bases, a window's prefix key, the search of a key group
 #include "collapse.inc.hip"   // collapseNoMismatch: the prefix-key join and the diagonal scan
 
 #include "taxonomy.inc.hip"   // assignTaxonomy: the per-(query, tile) sums and their fold

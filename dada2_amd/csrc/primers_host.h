@@ -6,39 +6,14 @@
 // complement of each), every letter a byte of plane selectors: the letter's IUPAC set for a primer with a letter beyond A/C/G/T
 // (fixed = FALSE, :111-112), the "is exactly this base" plane for a primer of A/C/G/T only.  Both rules are symmetric under
 // complement, so the reverse complement of a pattern is matched by the same rule and the read is never reverse-complemented.
-// The reads go up as dada2hip_filter_reads' do - pieces of at most PR_PIECE_READS reads / PR_PIECE_BYTES bytes
-// (DADA2HIP_PRIMERS_PIECE, DADA2HIP_PRIMERS_PIECE_BYTES: fewer, for the tests), two slots with pinned staging, device buffers and
-// a stream each, the copy of piece k + 1 under the kernel of piece k - but only the sequence bytes and the offsets; 32 bytes per
-// read come back, and 32 more when the starts are asked for.
+// The reads go up through read_pieces.h's two-slot pipeline (DADA2HIP_PRIMERS_PIECE, DADA2HIP_PRIMERS_PIECE_BYTES: smaller pieces,
+// for the tests), only the sequence bytes and the offsets, the slots made per call; the stage supplies the one kernel and the
+// scatter (32 bytes per read come back, 32 more when the starts are asked for).  From stage_common.h: the clocks, the end of a call.
 #pragma once
 
 namespace {
 
-constexpr int64_t PR_PIECE_READS = 1 << 16;
-constexpr int64_t PR_PIECE_BYTES = 32 << 20;
-
-enum { PS_IN = 0, PS_KEPT, PS_CODE1, PS_FLIPPED = 6, PS_MULTI, PS_HITS_FWD, PS_HITS_REV, PS_PIECES, PS_TILES, PS_BYTES, PS_US_UP, PS_US_KERNEL,
-       PS_US_DOWN, PS_US_PARSE, PS_US_DEFLATE, PS_US_WRITE, PS_US_TOTAL };
-
-struct PrSlot {
-  PinBuf<uint8_t> h_seq;
-  PinBuf<long long> h_off;
-  PinBuf<PrimerOut> h_out;
-  PinBuf<int32_t> h_starts;
-  DevBuf<uint8_t> d_seq;
-  DevBuf<long long> d_off;
-  DevBuf<PrimerOut> d_out;
-  DevBuf<int32_t> d_starts;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  int64_t first = 0, count = 0;
-  bool busy = false;
-  ~PrSlot() {
-    if (busy && st) (void)hipStreamSynchronize(st);
-    for (int i = 0; i < 2; i++) if (ev[i]) (void)hipEventDestroy(ev[i]);
-    if (st) (void)hipStreamDestroy(st);
-  }
-};
+using PrSlot = PieceSlot<PrimerOut, 2>;   // aux: the eight starts
 
 // the IUPAC set of a letter over A C G T = 1 2 4 8 (Biostrings' IUPAC_CODE_MAP); 0 for anything else
 inline int pr_iupac(char c) {
@@ -109,19 +84,14 @@ void primers_reads_body(int64_t n, const char *seq, const int64_t *offsets, cons
   st[PS_IN] = n;
   select_device(device);
   PrSlot slot[2];
-  for (PrSlot &S : slot) {
-    D2_HIP(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
-    for (int i = 0; i < 2; i++) D2_HIP(hipEventCreate(&S.ev[i]));
-  }
+  for (PrSlot &S : slot) S.create();
   int64_t bad_read = -1;
-  auto harvest = [&](PrSlot &S) {
-    if (!S.busy) return;
-    auto t0 = clk::now();
-    D2_HIP(hipStreamSynchronize(S.st));
-    S.busy = false;
-    D2_HIP(hipGetLastError());
-    float ms = 0.0f;
-    D2_HIP(hipEventElapsedTime(&ms, S.ev[0], S.ev[1])); st[PS_US_KERNEL] += (int64_t)((double)ms * 1e3);
+  auto launch = [&](PrSlot &S, int c) {
+    launch_primers(A, c, S.d_seq.p, S.d_off.p, S.d_out.p, starts ? S.d_aux.p : nullptr, S.st);
+    st[PS_PIECES]++;
+  };
+  auto scatter = [&](PrSlot &S) {
+    add_elapsed(st[PS_US_KERNEL], S.ev[0], S.ev[1]);
     const int64_t f = S.first, c = S.count;
     const PrimerOut *o = S.h_out.p;
     for (int64_t i = 0; i < c; i++) {
@@ -137,40 +107,11 @@ void primers_reads_body(int64_t n, const char *seq, const int64_t *offsets, cons
       st[PS_MULTI] += (x.hits[0] > 1 || x.hits[1] > 1 || x.hits[2] > 1 || x.hits[3] > 1) ? 1 : 0;
       st[PS_HITS_FWD] += x.hits[0]; st[PS_HITS_REV] += x.hits[1];
     }
-    if (starts) memcpy(starts + 8 * f, S.h_starts.p, (size_t)c * 8 * sizeof(int32_t));
-    st[PS_US_DOWN] += (int64_t)(ms_since(t0) * 1e3);
+    if (starts) memcpy(starts + 8 * f, S.h_aux.p, (size_t)c * 8 * sizeof(int32_t));
   };
-
-  const int64_t piece_reads = knobs().primers_piece > 0 ? std::min<int64_t>(knobs().primers_piece, PR_PIECE_READS) : PR_PIECE_READS;
-  const int64_t piece_bytes = knobs().primers_piece_bytes > 0 ? std::min<int64_t>(knobs().primers_piece_bytes, PR_PIECE_BYTES) : PR_PIECE_BYTES;
-  int64_t r0 = 0;
-  for (int piece = 0; r0 < n; piece++) {
-    int64_t r1 = r0 + 1;
-    while (r1 < n && r1 - r0 < piece_reads && offsets[r1 + 1] - offsets[r0] <= piece_bytes) r1++;
-    PrSlot &S = slot[piece & 1];
-    harvest(S);
-    auto t_up = clk::now();
-    const int64_t c = r1 - r0, base = offsets[r0], bytes = offsets[r1] - base;
-    S.h_seq.alloc((size_t)bytes); S.h_off.alloc((size_t)c + 1); S.h_out.alloc((size_t)c);
-    S.d_seq.alloc((size_t)bytes); S.d_off.alloc((size_t)c + 1); S.d_out.alloc((size_t)c);
-    if (starts) { S.h_starts.alloc((size_t)c * 8); S.d_starts.alloc((size_t)c * 8); }
-    parallel_for((size_t)bytes, (size_t)1 << 20, [&](size_t lo, size_t hi) { memcpy(S.h_seq.p + lo, seq + base + lo, hi - lo); });
-    for (int64_t i = 0; i <= c; i++) S.h_off.p[i] = (long long)(offsets[r0 + i] - base);
-    if (bytes > 0) D2_HIP(hipMemcpyAsync(S.d_seq.p, S.h_seq.p, (size_t)bytes, hipMemcpyHostToDevice, S.st));
-    D2_HIP(hipMemcpyAsync(S.d_off.p, S.h_off.p, (size_t)(c + 1) * 8, hipMemcpyHostToDevice, S.st));
-    D2_HIP(hipEventRecord(S.ev[0], S.st));
-    launch_primers(A, (int)c, S.d_seq.p, S.d_off.p, S.d_out.p, starts ? S.d_starts.p : nullptr, S.st);
-    D2_HIP(hipEventRecord(S.ev[1], S.st));
-    D2_HIP(hipMemcpyAsync(S.h_out.p, S.d_out.p, (size_t)c * sizeof(PrimerOut), hipMemcpyDeviceToHost, S.st));
-    if (starts) D2_HIP(hipMemcpyAsync(S.h_starts.p, S.d_starts.p, (size_t)c * 8 * sizeof(int32_t), hipMemcpyDeviceToHost, S.st));
-    S.first = r0; S.count = c; S.busy = true;
-    st[PS_BYTES] += bytes + (c + 1) * 8; st[PS_PIECES]++;
-    st[PS_US_UP] += (int64_t)(ms_since(t_up) * 1e3);
-    r0 = r1;
-  }
-  harvest(slot[0]); harvest(slot[1]);
-  st[PS_US_TOTAL] = (int64_t)(ms_since(t_call) * 1e3);
-  if (stats) memcpy(stats, st, sizeof st);
+  run_pieces(slot, n, seq, nullptr, offsets, knobs().primers_piece, knobs().primers_piece_bytes, starts ? 8 : 0, st, PS_BYTES, PS_US_UP,
+             PS_US_DOWN, launch, scatter);
+  finish_stats(st, PS_US_TOTAL, t_call, stats);
   if (bad_read >= 0)
     throw RuntimeErr{DADA2HIP_ERR_UNSUPPORTED, "dada2hip: read " + std::to_string(bad_read + 1) +
                                                    " holds a letter outside the upper-case IUPAC codes ACGTMRWSYKVHDBN."};

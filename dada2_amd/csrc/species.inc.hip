@@ -1,6 +1,6 @@
 // species.inc.hip — the device side of assignSpecies (R/taxonomy.R:264-280: PDict + vcountPDict > 0 per chunk of equal-length
 // queries, a second time over the reverse complements with tryRC); included by kernels.hip, inside namespace d2, behind
-// collapse.inc.hip (cl_bases16).
+// seqkeys.inc.hip (bases16, the window key and the search of a key group).
 //
 // The reference asks, for every (query, reference) pair, "does the query occur in the reference as a substring", fixed = TRUE:
 // a reference position with any letter other than upper-case A/C/G/T matches nothing.  Here the references are resident
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void k_species_seed(SpeciesRefs R, int r0, int
     const uint32_t *row = R.words + wo;
     for (int g = 0; g < K.ngroups; g++) {
       const int kl = K.groups[3 * g], first = K.groups[3 * g + 1], cnt = K.groups[3 * g + 2];
-      const unsigned long long mask = kl >= 32 ? ~0ull : ((1ull << (2 * kl)) - 1ull);
+      const unsigned long long mask = key_mask(kl);
       const uint32_t pmask = kl >= 32 ? ~0u : ((1u << kl) - 1u);
       const int npos = L - kl + 1;                           // windows that end inside this reference
       for (int p0 = 0; p0 < npos; p0 += 64) {                // (uniform over the wave: the ballot below is taken by all lanes)
@@ -68,15 +68,11 @@ __global__ __launch_bounds__(256) void k_species_seed(SpeciesRefs R, int r0, int
         int ki = 0;
         if (p < npos && (sp_bits32(R.nplane, wo * 16 + p) & pmask) == 0u) {
           nwin++;
-          const unsigned long long w = ((((unsigned long long)cl_bases16(row, nw, p + 16)) << 32) | cl_bases16(row, nw, p)) & mask;
+          const unsigned long long w = window_key(row, nw, p, mask);
           const uint32_t h = sp_hash(w, kl), ba = sp_bit_a(h), bb = sp_bit_b(h);
           if ((s_bm[ba >> 5] >> (ba & 31)) & (s_bm[bb >> 5] >> (bb & 31)) & 1u) {
             npast++;
-            int lo = first, hi = first + cnt;                // the first key >= w of the group
-            while (lo < hi) {
-              const int mid = (lo + hi) >> 1;
-              if (K.keys[mid] < w) lo = mid + 1; else hi = mid;
-            }
+            const int lo = key_lower_bound(K.keys, first, cnt, w);
             hit = lo < first + cnt && K.keys[lo] == w;
             ki = lo;
           }
@@ -119,7 +115,7 @@ __global__ __launch_bounds__(256) void k_species_verify(SpeciesRefs R, SpeciesKe
     const uint32_t *pw = K.pat_words + K.pat_woff[pt];
     for (int o = 32; o < pl && ok; o += 16) {                // bases 32.. (the key is bases 0..31)
       const int n = min(16, pl - o);
-      ok = ((pw[o >> 4] ^ cl_bases16(row, nw, c.pos + o)) & (n >= 16 ? ~0u : ((1u << (2 * n)) - 1u))) == 0u;
+      ok = ((pw[o >> 4] ^ bases16(row, nw, c.pos + o)) & (n >= 16 ? ~0u : ((1u << (2 * n)) - 1u))) == 0u;
     }
     if (ok) {
       const unsigned long long i = atomicAdd(&counters[3], 1ull);

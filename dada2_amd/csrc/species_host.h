@@ -10,7 +10,7 @@
 // what fits, and a range of references that counted more is halved and run again; a single reference that still counts more
 // runs with a buffer of the counted size.  The hit buffer starts at the same size and grows to the counted size.  The pairs are
 // sorted and repeats dropped on the host (several positions or both strands in one reference are one hit), then expanded to the
-// caller's queries.
+// caller's queries.  stage_common.h: acgt_code, revcomp_acgt, the prefix keys and their groups, Events, the clocks, finish_stats.
 #pragma once
 
 struct dada2hip_species {
@@ -34,8 +34,6 @@ namespace {
 
 constexpr int SP_KEY = 32;             // bases of a prefix key
 constexpr int SP_CHUNK_MAX = 8192;     // distinct queries per pass: at most 16 384 keys, two bits each, in the 2^18-bit bitmap (98.6 % of the misses stop there)
-
-inline int sp_base(char c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }
 
 struct SpPacked {
   std::vector<uint32_t> words, nplane;
@@ -62,7 +60,7 @@ void sp_pack_refs(int nref, const char *const *refs, SpPacked &P) {
       uint32_t *row = P.words.data() + P.woff[r], *pl = P.nplane.data() + P.woff[r] / 2;
       const char *s = refs[r];
       for (int i = 0; i < P.len[r]; i++) {
-        const int b = sp_base(s[i]);
+        const int b = acgt_code(s[i]);
         if (b < 0) pl[i >> 5] |= 1u << (i & 31);
         else row[i >> 4] |= (uint32_t)b << (2 * (i & 15));
       }
@@ -71,56 +69,40 @@ void sp_pack_refs(int nref, const char *const *refs, SpPacked &P) {
 }
 
 struct SpTables {
-  std::vector<unsigned long long> keys;
-  std::vector<int32_t> groups, key_pat_off, key_pats, pat_woff, pat_len, pat_query;
+  PrefixKeyTable K;                                             // keys, groups (key_of: per pattern)
+  std::vector<int32_t> key_pat_off, key_pats, pat_woff, pat_len, pat_query;
   std::vector<uint32_t> pat_words;
 };
 
 // the patterns of the distinct queries [q0, q1) of uq (A/C/G/T only, not empty); a pattern reports under its query's index in uq
 void sp_build_tables(const std::vector<std::string> &uq, size_t q0, size_t q1, bool try_rc, SpTables &T) {
   T = SpTables();
-  struct Ent { int kl; unsigned long long key; int pat; };
-  std::vector<Ent> ents;
-  std::string rc;
+  std::vector<PrefixKey> kp;                                    // per pattern
   auto add = [&](const std::string &s, size_t q) {
-    const int pat = (int)T.pat_len.size(), len = (int)s.size(), kl = std::min(len, SP_KEY);
+    const int len = (int)s.size();
     T.pat_woff.push_back((int32_t)T.pat_words.size()); T.pat_len.push_back(len); T.pat_query.push_back((int32_t)q);
     T.pat_words.resize(T.pat_words.size() + (size_t)(len + 15) / 16, 0u);
     uint32_t *w = T.pat_words.data() + T.pat_woff.back();
-    for (int i = 0; i < len; i++) w[i >> 4] |= (uint32_t)sp_base(s[i]) << (2 * (i & 15));
-    unsigned long long key = w[0];
-    if (kl > 16) key |= (unsigned long long)w[1] << 32;
-    if (kl < 32) key &= (1ull << (2 * kl)) - 1ull;
-    ents.push_back(Ent{kl, key, pat});
+    for (int i = 0; i < len; i++) w[i >> 4] |= (uint32_t)acgt_code(s[i]) << (2 * (i & 15));
+    kp.push_back(prefix_key(w, std::min(len, SP_KEY)));
   };
   for (size_t q = q0; q < q1; q++) {
     const std::string &s = uq[q];
     add(s, q);
     if (try_rc) {
-      rc.assign(s.rbegin(), s.rend());
-      for (char &c : rc) c = "TGCA"[sp_base(c)];
+      const std::string rc = revcomp_acgt(s);
       if (rc != s) add(rc, q);
     }
   }
   if (T.pat_words.size() > (size_t)INT32_MAX) throw RuntimeErr{DADA2HIP_ERR_RUNTIME, "dada2hip: a chunk of queries is too large."};
-  std::sort(ents.begin(), ents.end(), [](const Ent &a, const Ent &b) {
-    return a.kl != b.kl ? a.kl < b.kl : (a.key != b.key ? a.key < b.key : a.pat < b.pat);
-  });
-  for (size_t i = 0; i < ents.size(); i++) {
-    const bool new_group = i == 0 || ents[i].kl != ents[i - 1].kl;
-    if (new_group || ents[i].key != ents[i - 1].key) {
-      if (new_group) { T.groups.push_back(ents[i].kl); T.groups.push_back((int32_t)T.keys.size()); T.groups.push_back(0); }
-      T.groups.back()++;
-      T.keys.push_back(ents[i].key);
-      T.key_pat_off.push_back((int32_t)T.key_pats.size());
-    }
-    T.key_pats.push_back(ents[i].pat);
-  }
-  T.key_pat_off.push_back((int32_t)T.key_pats.size());
+  build_prefix_keys(kp, T.K);
+  // the patterns of every key, ascending inside a key: a counting sort of the patterns by key
+  T.key_pat_off.assign(T.K.keys.size() + 1, 0); T.key_pats.resize(kp.size());
+  for (int32_t k : T.K.key_of) T.key_pat_off[k + 1]++;
+  for (size_t k = 0; k < T.K.keys.size(); k++) T.key_pat_off[k + 1] += T.key_pat_off[k];
+  std::vector<int32_t> at(T.key_pat_off.begin(), T.key_pat_off.end() - 1);
+  for (size_t pat = 0; pat < kp.size(); pat++) T.key_pats[at[T.K.key_of[pat]]++] = (int32_t)pat;
 }
-
-enum { SS_REFS = 0, SS_BASES, SS_WINDOWS, SS_PAST_BITMAP, SS_CANDIDATES, SS_RERUNS, SS_HITS, SS_LAUNCHES, SS_US_SEED_HOST, SS_US_SEED_DEV,
-       SS_US_VERIFY_HOST, SS_US_VERIFY_DEV, SS_US_TOTAL, SS_BYTES };
 
 void species_open_body(int32_t nref, const char *const *refs, int32_t device, dada2hip_species **out, int64_t *stats) {
   auto t_call = clk::now();
@@ -139,11 +121,9 @@ void species_open_body(int32_t nref, const char *const *refs, int32_t device, da
   D2_HIP(hipMemcpy(m->nplane.p, P.nplane.data(), P.nplane.size() * 4, hipMemcpyHostToDevice));
   D2_HIP(hipMemcpy(m->woff.p, P.woff.data(), (size_t)nref * 8, hipMemcpyHostToDevice));
   D2_HIP(hipMemcpy(m->len.p, P.len.data(), (size_t)nref * 4, hipMemcpyHostToDevice));
-  if (stats) {
-    memset(stats, 0, DADA2HIP_SPECIES_NSTATS * sizeof(int64_t));
-    stats[SS_REFS] = nref; stats[SS_BASES] = P.nbases; stats[SS_US_TOTAL] = (int64_t)(ms_since(t_call) * 1e3);
-    stats[SS_BYTES] = (int64_t)((P.words.size() + P.nplane.size()) * 4 + (size_t)nref * 12);
-  }
+  int64_t st[DADA2HIP_SPECIES_NSTATS] = {0};
+  st[SS_REFS] = nref; st[SS_BASES] = P.nbases; st[SS_BYTES] = (int64_t)((P.words.size() + P.nplane.size()) * 4 + (size_t)nref * 12);
+  finish_stats(st, SS_US_TOTAL, t_call, stats);
   *out = m.release();
 }
 
@@ -163,7 +143,7 @@ void species_match_body(const dada2hip_species *m, int32_t nseq, const char *con
       if (!seqs[j]) throw InputError{"dada2hip: bad arguments"};
       if (!seqs[j][0]) throw InputError{"dada2hip: an empty query sequence."};
       for (const char *c = seqs[j]; *c; c++)
-        if (sp_base(*c) < 0) throw InputError{"Non-ACGT characters present in the query sequences."};   // taxonomy.R:254
+        if (acgt_code(*c) < 0) throw InputError{"Non-ACGT characters present in the query sequences."};   // taxonomy.R:254
       auto it = seen.emplace(seqs[j], (int32_t)uq.size());
       if (it.second) uq.emplace_back(seqs[j]);
       to_uq[j] = it.first->second;
@@ -185,23 +165,31 @@ void species_match_body(const dada2hip_species *m, int32_t nseq, const char *con
     DevBuf<uint32_t> d_pw, d_bitmap;
     DevBuf<SpCand> d_cand;
     d_counters.alloc(4); d_bitmap.alloc(SP_BITMAP_WORDS); d_cand.alloc((size_t)cap0); d_hits.alloc((size_t)cap0);
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 4; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ev};
-    for (int i = 0; i < 4; i++) D2_HIP(hipEventCreate(&ev[i]));
+    Events<4> ev;
+    ev.create();
     hipStream_t s = m->stream;
     unsigned long long cnt[4];
     auto up = [&](auto &d, const auto &h) {
       d.alloc(h.size());
       if (!h.empty()) D2_HIP(hipMemcpyAsync(d.p, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice, s));
     };
+    auto counted = [&](int e, int word, auto &&launch) {        // a launch between ev[e] and ev[e + 1], the counters back behind it
+      D2_HIP(hipEventRecord(ev[e], s));
+      launch();
+      D2_HIP(hipEventRecord(ev[e + 1], s));
+      D2_HIP(hipMemcpyAsync(cnt, d_counters.p, 4 * 8, hipMemcpyDeviceToHost, s));
+      sync_checked(s);
+      st[SS_LAUNCHES]++;
+      add_elapsed(st[word], ev[e], ev[e + 1]);
+    };
     SpTables T;
     std::vector<unsigned long long> got;
     for (size_t q0 = 0; q0 < uq.size(); q0 += chunk) {
       sp_build_tables(uq, q0, std::min(uq.size(), q0 + chunk), try_rc != 0, T);
-      up(d_keys, T.keys); up(d_groups, T.groups); up(d_kpo, T.key_pat_off); up(d_kp, T.key_pats); up(d_pwo, T.pat_woff);
+      up(d_keys, T.K.keys); up(d_groups, T.K.groups); up(d_kpo, T.key_pat_off); up(d_kp, T.key_pats); up(d_pwo, T.pat_woff);
       up(d_pl, T.pat_len); up(d_pq, T.pat_query); up(d_pw, T.pat_words);
       SpeciesKeys K;
-      K.keys = d_keys.p; K.groups = d_groups.p; K.ngroups = (int)(T.groups.size() / 3); K.nkeys = (int)T.keys.size();
+      K.keys = d_keys.p; K.groups = d_groups.p; K.ngroups = (int)(T.K.groups.size() / 3); K.nkeys = (int)T.K.keys.size();
       K.key_pat_off = d_kpo.p; K.key_pats = d_kp.p; K.pat_woff = d_pwo.p; K.pat_len = d_pl.p; K.pat_query = d_pq.p; K.pat_words = d_pw.p;
       D2_HIP(hipMemsetAsync(d_bitmap.p, 0, SP_BITMAP_WORDS * 4, s));
       launch_species_bitmap(K, d_bitmap.p, s);
@@ -213,15 +201,8 @@ void species_match_body(const dada2hip_species *m, int32_t nseq, const char *con
         // ---- seed ----
         auto t_seed = clk::now();
         D2_HIP(hipMemsetAsync(d_counters.p, 0, 4 * 8, s));
-        D2_HIP(hipEventRecord(ev[0], s));
-        launch_species_seed(R, r0, r1, K, d_bitmap.p, d_cand.p, (unsigned long long)d_cand.n, d_counters.p, s);
-        D2_HIP(hipEventRecord(ev[1], s));
-        D2_HIP(hipMemcpyAsync(cnt, d_counters.p, 4 * 8, hipMemcpyDeviceToHost, s));
-        D2_HIP(hipStreamSynchronize(s));
-        D2_HIP(hipGetLastError());
-        float ms = 0.0f;
-        D2_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        st[SS_LAUNCHES]++; st[SS_US_SEED_DEV] += (int64_t)((double)ms * 1e3); st[SS_US_SEED_HOST] += (int64_t)(ms_since(t_seed) * 1e3);
+        counted(0, SS_US_SEED_DEV, [&] { launch_species_seed(R, r0, r1, K, d_bitmap.p, d_cand.p, (unsigned long long)d_cand.n, d_counters.p, s); });
+        add_lap(st[SS_US_SEED_HOST], t_seed);
         const unsigned long long ncand = cnt[0];
         if (ncand > (unsigned long long)d_cand.n) {            // nothing of this launch is used
           st[SS_RERUNS]++;
@@ -240,14 +221,7 @@ void species_match_body(const dada2hip_species *m, int32_t nseq, const char *con
         auto t_ver = clk::now();
         for (;;) {
           D2_HIP(hipMemsetAsync(d_counters.p + 3, 0, 8, s));
-          D2_HIP(hipEventRecord(ev[2], s));
-          launch_species_verify(R, K, d_cand.p, ncand, d_hits.p, (unsigned long long)d_hits.n, d_counters.p, s);
-          D2_HIP(hipEventRecord(ev[3], s));
-          D2_HIP(hipMemcpyAsync(cnt, d_counters.p, 4 * 8, hipMemcpyDeviceToHost, s));
-          D2_HIP(hipStreamSynchronize(s));
-          D2_HIP(hipGetLastError());
-          D2_HIP(hipEventElapsedTime(&ms, ev[2], ev[3]));
-          st[SS_LAUNCHES]++; st[SS_US_VERIFY_DEV] += (int64_t)((double)ms * 1e3);
+          counted(2, SS_US_VERIFY_DEV, [&] { launch_species_verify(R, K, d_cand.p, ncand, d_hits.p, (unsigned long long)d_hits.n, d_counters.p, s); });
           if (cnt[3] <= (unsigned long long)d_hits.n) break;
           d_hits.alloc((size_t)cnt[3]);                        // (the candidates are still there: only this kernel runs again)
         }
@@ -258,7 +232,7 @@ void species_match_body(const dada2hip_species *m, int32_t nseq, const char *con
           got.erase(std::unique(got.begin(), got.end()), got.end());
           pairs.insert(pairs.end(), got.begin(), got.end());
         }
-        st[SS_US_VERIFY_HOST] += (int64_t)(ms_since(t_ver) * 1e3);
+        add_lap(st[SS_US_VERIFY_HOST], t_ver);
       }
     }
   }
@@ -278,8 +252,7 @@ void species_match_body(const dada2hip_species *m, int32_t nseq, const char *con
     for (int64_t i = uoff[to_uq[j]]; i < uoff[to_uq[j] + 1]; i++) *o++ = (int32_t)(uint32_t)pairs[(size_t)i];
   }
   st[SS_HITS] = H->offsets[nseq];
-  st[SS_US_TOTAL] = (int64_t)(ms_since(t_call) * 1e3);
-  if (stats) memcpy(stats, st, sizeof st);
+  finish_stats(st, SS_US_TOTAL, t_call, stats);
   *out = H.release();
 }
 

@@ -1,0 +1,27 @@
+// stage_stats.h — the words of the five stages' `stats` arrays (include/dada2hip.h says what each holds), named once.  Plain C++:
+// driver.cpp takes it through stage_common.h, derep.cpp - whose file-level entries add the calls' words up over the chunks of a
+// file - directly.  A word's position is ABI: a new word goes in front of its enum's *_COUNT, never between two others.
+#pragma once
+#include "../../include/dada2hip.h"
+
+enum { CS_NDEDUP = 0, CS_CAND, CS_SCANNED, CS_SCREENED_OUT, CS_BOUND, CS_ALIGNED, CS_HAM0, CS_BATCHES, CS_US_JOIN, CS_US_SCAN, CS_US_ALIGN,
+       CS_US_RESOLVE, CS_US_TOTAL, CS_COUNT };
+enum { TT_US_HOST = 0, TT_US_UPLOAD, TT_BYTES, TT_COUNT };     // dada2hip_taxonomy_train
+enum { TS_CLASSIFIED = 0, TS_SLAB, TS_GATHER, TS_FLIPPED, TS_LAUNCHES, TS_US_PREPARE, TS_US_SLAB, TS_US_GATHER, TS_US_ORIENT, TS_US_TOTAL,
+       TS_COUNT };
+enum { SS_REFS = 0, SS_BASES, SS_WINDOWS, SS_PAST_BITMAP, SS_CANDIDATES, SS_RERUNS, SS_HITS, SS_LAUNCHES, SS_US_SEED_HOST, SS_US_SEED_DEV,
+       SS_US_VERIFY_HOST, SS_US_VERIFY_DEV, SS_US_TOTAL, SS_BYTES, SS_COUNT };
+// FS_STAGE1 .. + 10: the reads dropped at stage 1..11; PS_CODE1 .. + 3: those with code 1..4.  *_US_PARSE and behind: the file level's.
+enum { FS_IN = 0, FS_KEPT, FS_STAGE1, FS_KEYS = 13, FS_LDS, FS_BYTES, FS_US_UP, FS_US_SCAN, FS_US_EE, FS_US_KMERS, FS_US_DOWN, FS_US_PARSE,
+       FS_US_DEFLATE, FS_US_WRITE, FS_US_TOTAL, FS_US_INFLATE, FS_COUNT };
+enum { PS_IN = 0, PS_KEPT, PS_CODE1, PS_FLIPPED = 6, PS_MULTI, PS_HITS_FWD, PS_HITS_REV, PS_PIECES, PS_TILES, PS_BYTES, PS_US_UP, PS_US_KERNEL,
+       PS_US_DOWN, PS_US_PARSE, PS_US_DEFLATE, PS_US_WRITE, PS_US_TOTAL, PS_US_INFLATE, PS_COUNT };
+// How a file adds its chunks' calls up.  Filter: the words of the context are taken, the call's total is the file's own, every other
+// word adds; of a pair's second file only the bytes and the call's clocks add.  Primers: every word of the call adds.
+enum { FS_TAKEN_FIRST = FS_KEYS, FS_TAKEN_LAST = FS_LDS, FS_CLOCK_FIRST = FS_BYTES, FS_CLOCK_LAST = FS_US_DOWN, PS_CALL_LAST = PS_US_DOWN };
+
+static_assert(CS_COUNT <= DADA2HIP_COLLAPSE_NSTATS && TT_COUNT <= DADA2HIP_TAXONOMY_NSTATS && TS_COUNT <= DADA2HIP_TAXONOMY_NSTATS &&
+              SS_COUNT <= DADA2HIP_SPECIES_NSTATS && FS_COUNT <= DADA2HIP_FILTER_NSTATS && PS_COUNT <= DADA2HIP_PRIMERS_NSTATS, "stats words");
+static_assert(FS_STAGE1 + 11 == FS_KEYS && PS_CODE1 + 4 == PS_FLIPPED, "the per-stage and per-code counts fill the gap left for them");
+static_assert(FS_TAKEN_LAST + 1 == FS_CLOCK_FIRST && FS_CLOCK_LAST + 1 == FS_US_PARSE, "filter: taken words, call clocks, file clocks in a row");
+static_assert(PS_CALL_LAST + 1 == PS_US_PARSE && FS_IN == PS_IN && FS_KEPT == PS_KEPT, "primers: the file's words follow the call's; reads in and kept as filter's");

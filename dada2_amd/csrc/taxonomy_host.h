@@ -8,8 +8,8 @@
 // reference's bits only over a table that is bit-equal to its table.  cnt is a float the reference increments, exact below 2^24
 // references.  On the device the table lies k-mer-major, T[kmer][genus padded to 64] (taxonomy.inc.hip).
 // A call of the classifier prepares, per query, its sorted valid k-mers (tax_karray, :55-71) and the replicate positions
-// (int)(arraylen * u) with u read in the reference's layout (:181-186: query j starts at unifs[j * max_arraylen] - neighbours
-// overlap), runs the kernels over chunks of queries, and counts `boot` on the host (:189-195).
+// (int)(arraylen * u) with u in the reference's layout (:181-186: query j starts at unifs[j * max_arraylen] - neighbours overlap),
+// runs the kernels over chunks of queries, counts `boot` on the host (:189-195).  stage_common.h: acgt_code, Events, the clocks.
 #pragma once
 
 struct dada2hip_taxonomy {
@@ -26,8 +26,6 @@ namespace {
 constexpr int TAX_K = 8, TAX_NKMER = 1 << (2 * TAX_K), TAX_NBOOT = 100, TAX_NPASS = TAX_NBOOT + 1, TAX_MIN_LEN = 50;
 constexpr int TAX_SLAB_MAX = 512;     // 128 KB of the 160 KB of LDS a workgroup can have
 
-inline int tax_base(char c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }
-
 // the valid 8-mer indices of s (of its reverse complement with rc), sorted ascending, duplicates kept; a k-mer with a letter
 // outside ACGT in it is skipped (tax_kmer returns -1)
 void tax_karray(const char *s, int len, bool rc, std::vector<uint16_t> &out) {
@@ -35,7 +33,7 @@ void tax_karray(const char *s, int len, bool rc, std::vector<uint16_t> &out) {
   uint32_t w = 0;
   int run = 0;
   for (int i = 0; i < len; i++) {
-    int b = tax_base(rc ? s[len - 1 - i] : s[i]);
+    int b = acgt_code(rc ? s[len - 1 - i] : s[i]);
     if (b < 0) { run = 0; continue; }
     if (rc) b = 3 - b;
     w = ((w << 2) | (uint32_t)b) & (TAX_NKMER - 1);
@@ -133,12 +131,11 @@ void taxonomy_train_body(int32_t nref, const char *const *refs, const int32_t *r
   D2_HIP(hipMemcpy(m->T.p, T.data(), T.size() * sizeof(float), hipMemcpyHostToDevice));
   if (stats) {
     memset(stats, 0, DADA2HIP_TAXONOMY_NSTATS * sizeof(int64_t));
-    stats[0] = (int64_t)(ms_host * 1e3); stats[1] = (int64_t)((ms_since(t_call) - ms_host) * 1e3); stats[2] = (int64_t)(T.size() * sizeof(float));
+    stats[TT_US_HOST] = (int64_t)(ms_host * 1e3); stats[TT_US_UPLOAD] = (int64_t)((ms_since(t_call) - ms_host) * 1e3);
+    stats[TT_BYTES] = (int64_t)(T.size() * sizeof(float));
   }
   *out = m.release();
 }
-
-enum { TS_CLASSIFIED = 0, TS_SLAB, TS_GATHER, TS_FLIPPED, TS_LAUNCHES, TS_US_PREPARE, TS_US_SLAB, TS_US_GATHER, TS_US_ORIENT, TS_US_TOTAL };
 
 struct TaxQuery {
   int32_t id;                          // the caller's index
@@ -164,10 +161,8 @@ double taxonomy_run(const dada2hip_taxonomy *m, const std::vector<TaxQuery> &Q, 
   std::vector<int32_t> koff, qid;
   std::vector<long long> boff;
   std::vector<uint16_t> karr, bpos;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  D2_HIP(hipEventCreate(&e0));
-  D2_HIP(hipEventCreate(&e1));
-  struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evg{e0, e1};
+  Events<2> ev;
+  ev.create();
   double us = 0.0;
   for (size_t c0 = 0; c0 < list.size(); c0 += chunk) {
     const size_t nq = std::min(chunk, list.size() - c0);
@@ -196,18 +191,17 @@ double taxonomy_run(const dada2hip_taxonomy *m, const std::vector<TaxQuery> &Q, 
     J.koff = d_koff.p; J.karr = d_karr.p; J.boff = d_boff.p; J.bpos = d_bpos.p; J.qid = d_qid.p;
     J.seed_lo = (uint32_t)seed; J.seed_hi = (uint32_t)(seed >> 32);
     J.part = d_part.p; J.best = d_best.p; J.ntie = d_ntie.p; J.winner = d_winner.p;
-    D2_HIP(hipEventRecord(e0, m->stream));
+    D2_HIP(hipEventRecord(ev[0], m->stream));
     if (!(slab && launch_tax_sums(J, std::max(max_a, 1), m->stream))) launch_tax_sums(J, 0, m->stream);
-    D2_HIP(hipEventRecord(e1, m->stream));
+    D2_HIP(hipEventRecord(ev[1], m->stream));
     launch_tax_combine(J, m->stream);
     launches += 2;
     D2_HIP(hipMemcpyAsync(best.data() + c0 * npass, d_best.p, nq * npass * 4, hipMemcpyDeviceToHost, m->stream));
     D2_HIP(hipMemcpyAsync(ntie.data() + c0 * npass, d_ntie.p, nq * npass * 4, hipMemcpyDeviceToHost, m->stream));
     D2_HIP(hipMemcpyAsync(winner.data() + c0 * npass, d_winner.p, nq * npass * 4, hipMemcpyDeviceToHost, m->stream));
-    D2_HIP(hipStreamSynchronize(m->stream));
-    D2_HIP(hipGetLastError());
+    sync_checked(m->stream);
     float ms = 0.0f;
-    D2_HIP(hipEventElapsedTime(&ms, e0, e1));
+    D2_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
     us += (double)ms * 1e3;
   }
   return us;
@@ -261,7 +255,7 @@ void taxonomy_assign_body(const dada2hip_taxonomy *m, int32_t nseq, const char *
   if (bad_unif.load() == 1) throw InputError{"dada2hip: a bootstrap uniform lies outside [0, 1)."};
   if (bad_unif.load() == 2) throw RuntimeErr{DADA2HIP_ERR_RUNTIME, "dada2hip: the bootstrap uniforms do not cover a query."};
   st[TS_CLASSIFIED] = (int64_t)Q.size();
-  st[TS_US_PREPARE] = (int64_t)(ms_since(t_call) * 1e3);
+  add_lap(st[TS_US_PREPARE], t_call);
 
   select_device(m->device);
   const int slab_max = std::min(std::max(knobs().tax_slab, 0), TAX_SLAB_MAX);
@@ -301,8 +295,7 @@ void taxonomy_assign_body(const dada2hip_taxonomy *m, int32_t nseq, const char *
       }
     }
   }
-  st[TS_US_TOTAL] = (int64_t)(ms_since(t_call) * 1e3);
-  if (stats) memcpy(stats, st, sizeof st);
+  finish_stats(st, TS_US_TOTAL, t_call, stats);
 }
 
 }  // namespace
