@@ -125,7 +125,18 @@ EXPORTS = [
     "dada2hip_species_hits_refs", "dada2hip_species_hits_free",
     "dada2hip_filter_open", "dada2hip_filter_free", "dada2hip_filter_reads", "dada2hip_filter_fastq", "dada2hip_filter_fastq_paired",
     "dada2hip_primers_reads", "dada2hip_primers_fastq",
+    "dada2hip_derep_combine", "dada2hip_sample_set_prior_seqs", "dada2hip_sample_prior_seqs_stats",
 ]
+
+PRIOR_SEQS_NSTATS = 16   # DADA2HIP_PRIOR_SEQS_NSTATS
+# the int64 words of dada2hip_sample_prior_seqs_stats, in order
+PRIOR_SEQS_STATS = ("given", "kept", "keys", "keys_in_lds", "flags_set", "blocks", "pack_us", "device_us", "kernel_device_us", "total_us")
+
+
+class CDerepView(C.Structure):
+    """dada2hip_derep_view"""
+    _fields_ = [("nuniques", C.c_int32), ("maxlen", C.c_int32), ("nreads", C.c_int64), ("seqs", C.c_void_p),
+                ("abundances", C.c_void_p), ("quals", C.c_void_p), ("map", C.c_void_p)]
 
 COLLAPSE_NSTATS = 16   # DADA2HIP_COLLAPSE_NSTATS
 # the int64 words of dada2hip_collapse_nomismatch's stats, in order (the *_us entries are host wall time in microseconds)
@@ -341,6 +352,10 @@ def lib():
     L.dada2hip_primers_reads.argtypes = [C.c_int64, vp, vp, C.POINTER(CPrimerParams), ip, vp, vp, vp, vp, vp, vp, vp, cp, C.c_size_t]
     L.dada2hip_primers_fastq.argtypes = [cp, cp, C.POINTER(CPrimerParams), ip, C.c_int64, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                          vp, cp, C.c_size_t]
+    L.dada2hip_derep_combine.argtypes = [ip, C.POINTER(CDerepView), C.POINTER(vp), vp, cp, C.c_size_t]
+    L.dada2hip_sample_set_prior_seqs.argtypes = [vp, ip, vp, vp, vp, C.POINTER(ip), cp, C.c_size_t]
+    L.dada2hip_sample_prior_seqs_stats.argtypes = [vp, vp]
+    L.dada2hip_sample_prior_seqs_stats.restype = None
     L.dada2hip_trim_cache.argtypes = []
     L.dada2hip_trim_cache.restype = None
     _lib = L

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib
 from .io import Derep, extend_err
-from .opts import COpts, DadaOpts, DadaResult
+from .opts import COpts, DadaOpts, DadaResult, NA_INTEGER
 
 _EB = 2048
 
@@ -201,6 +201,22 @@ class NativeDerep:
         mp[mp == np.iinfo(np.int32).min] = -1
         return Derep(seqs, ab, q, mp)
 
+    @classmethod
+    def _from_handle(cls, h):
+        """A dada2hip_derep the library handed out (dada2hip_derep_combine)."""
+        L = _lib.lib()
+        self = cls.__new__(cls)
+        self._h = h
+        self.nuniques = L.dada2hip_derep_nuniques(h)
+        self.nreads = L.dada2hip_derep_nreads(h)
+        self.maxlen = L.dada2hip_derep_maxlen(h)
+        return self
+
+    def qmax(self) -> int:
+        """``ceiling(max(derep$quals, na.rm=TRUE))`` (R/dada.R:290), over the library's matrix in place."""
+        q = np.ctypeslib.as_array(_lib.lib().dada2hip_derep_quals(self._h), (self.nuniques, self.maxlen))
+        return int(np.ceil(np.nanmax(q)))
+
     def close(self):
         if getattr(self, "_h", None):
             _lib.lib().dada2hip_derep_free(self._h)
@@ -211,6 +227,79 @@ class NativeDerep:
             self.close()
         except Exception:
             pass
+
+
+class _StrArray:
+    """``const char *const *`` over one NUL-separated blob (HostInput's layout)."""
+
+    def __init__(self, seqs):
+        parts = [s if isinstance(s, bytes) else str(s).encode("ascii") for s in seqs]
+        n = len(parts)
+        self.n = n
+        self._blob = b"\0".join(parts) + b"\0"
+        lens = np.fromiter((len(x) for x in parts), dtype=np.int64, count=n)
+        off = np.zeros(n, dtype=np.int64)
+        if n > 1:
+            np.cumsum(lens[:-1] + 1, out=off[1:])
+        self._ptrs = (off + np.frombuffer(self._blob, dtype=np.uint8).ctypes.data).astype(np.uint64)
+        self.p = self._ptrs.ctypes.data if n else None
+
+
+def _derep_view(d, keep):
+    """The dada2hip_derep_view of a Derep or a NativeDerep; what it points to is appended to ``keep``."""
+    L = _lib.lib()
+    v = _lib.CDerepView()
+    if isinstance(d, NativeDerep):
+        v.nuniques, v.maxlen, v.nreads = d.nuniques, d.maxlen, d.nreads
+        v.seqs = C.cast(L.dada2hip_derep_seqs(d._h), C.c_void_p)
+        v.abundances = C.cast(L.dada2hip_derep_abundances(d._h), C.c_void_p)
+        v.quals = C.cast(L.dada2hip_derep_quals(d._h), C.c_void_p)
+        v.map = C.cast(L.dada2hip_derep_map(d._h), C.c_void_p) if d.nreads else None
+        keep.append(d)
+        return v
+    if not isinstance(d, Derep):
+        raise ValueError("Requires derep-class objects.")
+    sa = _StrArray(d.seqs)
+    ab = np.ascontiguousarray(d.abundances, dtype=np.int32)
+    q = np.ascontiguousarray(d.quals, dtype=np.float64)
+    if q.ndim != 2 or q.shape[0] != sa.n or ab.shape != (sa.n,):
+        raise ValueError("derep$quals matrices must have one row for each derep$unique sequence.")
+    mp = np.array(d.map, dtype=np.int32, copy=True).ravel()
+    mp[mp < 0] = NA_INTEGER                                     # the numpy Derep's -1 (and the library's NA) both mean NA
+    keep.extend((sa, ab, q, mp))
+    v.nuniques, v.maxlen, v.nreads = sa.n, q.shape[1], mp.size
+    v.seqs, v.abundances, v.quals = sa.p, ab.ctypes.data, q.ctypes.data
+    v.map = mp.ctypes.data if mp.size else None
+    return v
+
+
+def _combine_native(dereps):
+    """dada2hip_derep_combine -> (NativeDerep of the pooled object, [unique_to_pool per sample])."""
+    dereps = list(dereps)
+    if not dereps:
+        raise ValueError("Requires derep-class objects.")
+    keep = []
+    views = (_lib.CDerepView * len(dereps))(*[_derep_view(d, keep) for d in dereps])
+    sizes = [int(v.nuniques) for v in views]
+    u2p = np.zeros(max(sum(sizes), 1), dtype=np.int32)
+    h = C.c_void_p()
+    eb = C.create_string_buffer(_EB)
+    _lib.check(_lib.lib().dada2hip_derep_combine(len(dereps), views, C.byref(h), u2p.ctypes.data, eb, _EB), eb)
+    cuts = np.cumsum([0] + sizes)
+    return NativeDerep._from_handle(h), [u2p[cuts[i]:cuts[i + 1]].copy() for i in range(len(sizes))]
+
+
+def combine_dereps(dereps):
+    """combineDereps2 (R/multiSample.R:165-203) through dada2hip_derep_combine: ``(Derep, [unique_to_pool per sample])``.  The pooled
+    uniques are the union of the samples' in order of first appearance, stably ordered by decreasing summed abundance; a quality is
+    the abundance-weighted mean of the samples' (NaN past a unique's length and past a narrower sample's width); the map is the
+    samples' maps one after the other, renumbered (-1 = NA, as in every numpy ``Derep``).  ``unique_to_pool[i][j]`` is the 0-based
+    pooled row of unique j of sample i.  ``dereps``: ``Derep`` and ``NativeDerep`` objects, mixed as they come."""
+    nd, u2p = _combine_native(dereps)
+    try:
+        return nd.to_derep(), u2p
+    finally:
+        nd.close()
 
 
 def derep_fastq(path: str, n: int = 10**6, qual_offset: int = 0) -> Derep:
@@ -258,6 +347,30 @@ class Sample:
         eb = C.create_string_buffer(_EB)
         pr = np.ascontiguousarray(priors, dtype=np.uint8)
         _lib.check(_lib.lib().dada2hip_sample_set_priors(self._h, pr.ctypes.data, eb, _EB), eb)
+
+    def set_prior_seqs(self, seqs, or_flags=None, want_match=False):
+        """dada2hip_sample_set_prior_seqs: flag the resident uniques whose sequence is one of ``seqs`` (``names(uniques) %in% seqs``,
+        R/dada.R:335; matched on the device), OR-ed with the per-unique ``or_flags`` where given.  Entries with a letter outside
+        A/C/G/T match nothing; duplicates are allowed.  Returns the number of flags set, or with ``want_match``
+        ``(nset, first_match)``: per unique the smallest index into ``seqs`` of an equal entry, -1 for none."""
+        sa = _StrArray(seqs)
+        orf = None
+        if or_flags is not None:
+            orf = np.ascontiguousarray(np.asarray(or_flags) != 0, dtype=np.uint8)
+            if orf.shape != (self.nraw,):
+                raise ValueError("or_flags must have one entry per unique.")
+        fm = np.full(self.nraw, -1, dtype=np.int32) if want_match else None
+        nset = C.c_int32(0)
+        eb = C.create_string_buffer(_EB)
+        _lib.check(_lib.lib().dada2hip_sample_set_prior_seqs(self._h, sa.n, sa.p, orf.ctypes.data if orf is not None else None,
+                                                             fm.ctypes.data if fm is not None else None, C.byref(nset), eb, _EB), eb)
+        return (int(nset.value), fm) if want_match else int(nset.value)
+
+    def prior_seqs_stats(self) -> dict:
+        """The words of this sample's last ``set_prior_seqs`` call (_lib.PRIOR_SEQS_STATS)."""
+        st = np.zeros(_lib.PRIOR_SEQS_NSTATS, dtype=np.int64)
+        _lib.lib().dada2hip_sample_prior_seqs_stats(self._h, st.ctypes.data)
+        return {k: int(st[i]) for i, k in enumerate(_lib.PRIOR_SEQS_STATS)}
 
     def run(self, err, opts: DadaOpts = None, *, max_clust=None, multithread=False, verbose=False,
             copts: COpts = None, log=None, should_abort=None) -> DadaResult:
@@ -1341,8 +1454,49 @@ def noqual_errfun(trans, pseudocount=1):
     return err
 
 
+def pseudo_priors_of(results, opts: DadaOpts):
+    """R/dada.R:399-400: the columns of makeSequenceTable over a pass's clusterings found in at least ``PSEUDO_PREVALENCE`` samples
+    or with at least ``PSEUDO_ABUNDANCE`` reads in all."""
+    mat, seqs = make_sequence_table(list(results))
+    hit = ((mat > 0).sum(axis=0) >= opts.PSEUDO_PREVALENCE) | (mat.sum(axis=0, dtype=np.int64) >= opts.PSEUDO_ABUNDANCE)
+    return [s for s, h in zip(seqs, hit) if h]
+
+
+def split_pooled(res: DadaResult, abundances, unique_to_pool) -> DadaResult:
+    """One input sample's share of a pooled result (R/dada.R:451-472).  ``unique_to_pool``: the 0-based pooled row of each of the
+    sample's uniques, ``abundances`` theirs.  The clusters some unique of the sample maps to are kept (NA is ignored) and
+    renumbered by ``cumsum(keep)``; clustering rows, clusterquals columns and the birth_subs rows of kept clusters are pruned,
+    ``birth_subs["clust"]`` and the map renumbered (NA kept), and ``clustering["abundance"]`` becomes the per-cluster sums of THIS
+    sample's abundances.  Everything else stays the pooled run's, exactly as in R: n0, n1, nunq, pval, the birth_* columns
+    (``birth_from`` still counts POOLED clusters), subqual and the per-unique pval vector (one entry per POOLED unique); the
+    quality columns are "not the qualities for this sample alone" (:462)."""
+    m = np.asarray(res.map, dtype=np.int64)[np.asarray(unique_to_pool, dtype=np.int64)]
+    ok = m != NA_INTEGER
+    nclust = res.nclust
+    keep = np.zeros(nclust, dtype=bool)
+    keep[m[ok] - 1] = True
+    new_bi = np.cumsum(keep)
+    clustering = {}
+    for c, v in res.clustering.items():
+        clustering[c] = [s for s, k in zip(v, keep) if k] if c == "sequence" else np.asarray(v)[keep].copy()
+    new_map = np.full(m.shape, NA_INTEGER, dtype=np.int32)
+    new_map[ok] = new_bi[m[ok] - 1]
+    sums = np.zeros(int(keep.sum()), dtype=np.int64)
+    np.add.at(sums, new_map[ok].astype(np.int64) - 1, np.asarray(abundances, dtype=np.int64)[ok])   # tapply(uniques, map, sum), :470
+    clustering["abundance"] = sums.astype(np.int32)
+    bc = np.asarray(res.birth_subs["clust"], dtype=np.int64)
+    bkeep = keep[bc - 1] if bc.size else np.zeros(0, dtype=bool)
+    birth_subs = {}
+    for c, v in res.birth_subs.items():
+        birth_subs[c] = [x for x, k in zip(v, bkeep) if k] if c in ("ref", "sub") else np.asarray(v)[bkeep].copy()
+    birth_subs["clust"] = new_bi[bc[bkeep] - 1].astype(np.int32)
+    return DadaResult(clustering, birth_subs, np.array(res.subqual, copy=True), np.asarray(res.clusterquals)[:, keep].copy(), new_map,
+                      np.array(res.pval, copy=True), dict(res.stats))
+
+
 def dada(dereps, err=None, *, self_consist=False, err_fun=noqual_errfun, opts: DadaOpts = None, priors=None,
-         device: int = 0, verbose=False, samples=None, timings: list = None, host_input=None, on_pass=None):
+         device: int = 0, verbose=False, samples=None, timings: list = None, host_input=None, on_pass=None, pool=False,
+         prior_seqs=None):
     """The sample loop and selfConsist loop of R/dada.R:256-405 over resident samples.
 
     ``err_fun`` maps the accumulated 16 x Q transition counts to a new error matrix; the
@@ -1350,11 +1504,63 @@ def dada(dereps, err=None, *, self_consist=False, err_fun=noqual_errfun, opts: D
     deterministic ``noqualErrfun`` stands in.  Returns (list[DadaResult], err_out,
     list of err matrices tried).  ``on_pass(k, errs_used, max_clust, results)`` is called after every pass with the
     error matrix each sample was run with (the all-ones start of R/dada.R:298 included) - the parity tests check every
-    pass of the loop through it, not just the last."""
+    pass of the loop through it, not just the last.
+
+    ``dereps``: a ``Derep`` or a list of them; a ``NativeDerep`` (the library's own object, from ``NativeDerep(path)``) stands wherever a
+    ``Derep`` does and is made resident without a host copy (``Sample.from_native``) - the pooled object of ``pool=True`` is one.
+
+    ``prior_seqs``: R's ``priors`` argument, a list of sequences (:149, :183, :335); they are matched against each resident
+    sample on the device (``Sample.set_prior_seqs``) and OR-ed with the per-unique flags ``priors[i]`` where both are given.
+
+    ``pool`` (:185-196): ``True`` combines the dereps (``combine_dereps``), runs the pass loop on ONE resident sample of the pooled
+    object and splits the result back (``split_pooled``, which says what stays the pooled run's): one DadaResult per INPUT
+    sample; per-sample ``priors`` flags, ``samples=`` and ``host_input=`` make no sense there and are a ValueError; ``on_pass``
+    sees the pooled sample.  With one derep it is ``False`` (:187).  ``"pseudo"`` keeps the samples separate: after every pass
+    with nconsist >= 1 the sequences found in ``PSEUDO_PREVALENCE`` samples or with ``PSEUDO_ABUNDANCE`` reads become priors of
+    the next pass, and the loop may end only at nconsist >= 2 (:391-404) - so without ``self_consist`` the second pass runs with
+    the matrix ``err_fun`` estimated from the first (:264, :300, :374), not with the caller's, and ``err_fun=None`` is a
+    ValueError."""
     o = (opts or DadaOpts()).normalised()
-    single = isinstance(dereps, Derep)
+    single = isinstance(dereps, (Derep, NativeDerep))
     if single:
         dereps = [dereps]
+    pseudo = False
+    if len(dereps) <= 1:                                           # :187
+        pool = False
+    if isinstance(pool, (bool, np.bool_)):
+        pool = bool(pool)
+    elif isinstance(pool, str) and pool == "pseudo":               # :193-195
+        pool, pseudo = False, True
+    else:
+        raise ValueError("Invalid pool argument.")
+    if pseudo and err_fun is None:
+        raise ValueError('pool="pseudo" runs its second pass with the error matrix err_fun estimates from the first: err_fun is required.')
+    prior_seqs = None if prior_seqs is None else [str(s) for s in prior_seqs]
+    if pool:
+        if priors is not None or samples is not None or host_input is not None:
+            raise ValueError("pool=True runs one pooled sample: per-sample priors, samples= and host_input= do not apply (use prior_seqs).")
+        import time
+        inputs = list(dereps)
+        t_create = time.perf_counter()
+        pooled, u2p = _combine_native(inputs)
+        try:
+            smp = Sample.from_native(pooled, None, device)
+            inner = None if timings is None else []
+            try:
+                res, err_out, errs = dada([pooled], err, self_consist=self_consist, err_fun=err_fun, opts=opts, device=device, verbose=verbose,
+                                          samples=[smp], timings=inner, on_pass=on_pass, prior_seqs=prior_seqs)
+            finally:
+                if timings is not None:                             # [0] = the combine and the upload of the pooled sample
+                    timings.extend([(time.perf_counter() - t_create) * 1e3 - sum(inner)] + inner[1:])
+                smp.close()
+        finally:
+            pooled.close()
+
+        def ab(d):
+            if isinstance(d, NativeDerep):
+                return np.ctypeslib.as_array(_lib.lib().dada2hip_derep_abundances(d._h), (d.nuniques,)).copy()
+            return d.abundances
+        return [split_pooled(res[0], ab(d), u) for d, u in zip(inputs, u2p)], err_out, errs
     import time
     own = samples is None
     t_create = time.perf_counter()
@@ -1362,7 +1568,8 @@ def dada(dereps, err=None, *, self_consist=False, err_fun=noqual_errfun, opts: D
         if host_input is not None and single:          # inputs already marshalled (bench.py): one resident sample from them
             samples = [Sample(host_input, None, None, None, device)]
         else:
-            samples = [Sample.from_derep(d, None if priors is None else priors[i], device) for i, d in enumerate(dereps)]
+            samples = [Sample.from_native(d, None if priors is None else priors[i], device) if isinstance(d, NativeDerep) else
+                       Sample.from_derep(d, None if priors is None else priors[i], device) for i, d in enumerate(dereps)]
     if timings is not None:
         timings.append((time.perf_counter() - t_create) * 1e3)   # [0] = making the samples resident (upload), then one entry per pass
     initialize = self_consist and err is None
@@ -1372,7 +1579,13 @@ def dada(dereps, err=None, *, self_consist=False, err_fun=noqual_errfun, opts: D
     # statement inside the pass loop it re-read the whole maxlen x nraw double matrix every pass (2 GB at 10^6 uniques: 70 ms of
     # every selfConsist pass, profiles/r09a_selfconsist_passes.txt)
     qmaxes = [d.qmax() for d in dereps]
+
+    def flag_by_sequence(seqs):                                     # names(uniques) %in% c(priors, pseudo_priors), :335
+        for i, smp in enumerate(samples):
+            smp.set_prior_seqs(seqs, or_flags=None if priors is None else priors[i])
     try:
+        if prior_seqs is not None:
+            flag_by_sequence(prior_seqs)
         while True:
             if nconsist > 0:
                 errs.append(np.array(err, copy=True))
@@ -1393,7 +1606,10 @@ def dada(dereps, err=None, *, self_consist=False, err_fun=noqual_errfun, opts: D
                 new_err[[0, 5, 10, 15], :] = 1.0                                                   # R/dada.R:385-388
             err = new_err
             if (not self_consist) or any(np.array_equal(e, err) for e in errs) or nconsist >= o.MAX_CONSIST:
-                break
+                if not pseudo or nconsist >= 2:                     # :392: a pseudo-pooled run needs one full pass for its priors
+                    break
+            if pseudo and nconsist >= 1:                            # :398-402
+                flag_by_sequence((prior_seqs or []) + pseudo_priors_of(results, o))
             nconsist += 1
     finally:
         if own:

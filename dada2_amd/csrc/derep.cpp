@@ -581,6 +581,152 @@ int dada2hip_sample_from_derep(const dada2hip_derep *d, const uint8_t *priors, i
 
 }  // extern "C"
 
+// ---- pooling: combineDereps2 (R/multiSample.R:165-203) ------------------------------------------------------------------------------
+// The union, the order and the renumbering are pool_plain.h's (plain C++, checked alone by tools/pool_plain_check.cpp); here are the
+// hashes (seq_hash over the host pool), the quality rows and the maps.  A quality is acc = acc + q * count per contributing sample
+// and acc / total at the end, as sweep(..., "*"), `+` and sweep(..., "/") do it in R: the multiply and the add are two roundings.
+// This translation unit is built with -ffp-contract=off (Makefile, FLAGS), so the loop below cannot become a fused multiply-add.
+#include "pool_plain.h"
+
+namespace {
+
+int derep_combine_body(int32_t nsamples, const dada2hip_derep_view *in, dada2hip_derep **out, int32_t *unique_to_pool, char *errbuf,
+                       size_t errlen) {
+  if (out) *out = nullptr;
+  if (!out || nsamples <= 0 || !in) { set_err(errbuf, errlen, "Requires derep-class objects."); return DADA2HIP_ERR_INPUT; }
+  d2::knobs_reload();
+  using dclk = std::chrono::steady_clock;
+  auto t_lap = dclk::now();
+  double ms_phase[5] = {0, 0, 0, 0, 0};                        // hashes, union, order, rows, maps (DADA2HIP_DEREP_TIMES=1)
+  auto lap = [&](int k) { ms_phase[k] = std::chrono::duration<double, std::milli>(dclk::now() - t_lap).count(); t_lap = dclk::now(); };
+  size_t nall = 0;
+  int64_t nreads = 0;
+  int32_t maxlen = 0;
+  for (int32_t s = 0; s < nsamples; s++) {
+    const dada2hip_derep_view &v = in[s];
+    if (v.nuniques < 0 || v.maxlen < 0 || v.nreads < 0 || (v.nuniques > 0 && (!v.seqs || !v.abundances || !v.quals)) || (v.nreads > 0 && !v.map)) {
+      set_err(errbuf, errlen, ("dada2hip: derep object " + std::to_string(s + 1) + " is incomplete.").c_str());
+      return DADA2HIP_ERR_INPUT;
+    }
+    nall += (size_t)v.nuniques; nreads += v.nreads; maxlen = std::max(maxlen, v.maxlen);
+  }
+  if (nall > (size_t)INT32_MAX) { set_err(errbuf, errlen, "dada2hip: too many unique sequences to pool."); return DADA2HIP_ERR_INPUT; }
+  // lengths and hashes of every unique of every sample, over the pool
+  std::vector<size_t> first((size_t)nsamples + 1, 0);
+  for (int32_t s = 0; s < nsamples; s++) first[s + 1] = first[s] + (size_t)in[s].nuniques;
+  std::vector<uint32_t> len(nall);
+  std::vector<uint64_t> hash(nall);
+  std::vector<PoolSample> S((size_t)nsamples);
+  std::atomic<int> bad{0};
+  for (int32_t s = 0; s < nsamples; s++) {
+    const dada2hip_derep_view &v = in[s];
+    uint32_t *l = len.data() + first[s];
+    uint64_t *h = hash.data() + first[s];
+    d2::parallel_for((size_t)v.nuniques, 2048, [&](size_t j0, size_t j1) {
+      for (size_t j = j0; j < j1; j++) {
+        const size_t n = v.seqs[j] ? strlen(v.seqs[j]) : 0;
+        if (n == 0 || n > (size_t)INT32_MAX || v.abundances[j] < 0) { bad.store(1, std::memory_order_relaxed); l[j] = 0; h[j] = 0; continue; }
+        l[j] = (uint32_t)n;
+        h[j] = seq_hash(v.seqs[j], n);
+      }
+    });
+    S[s].n = v.nuniques; S[s].seqs = v.seqs; S[s].len = l; S[s].hash = h; S[s].abund = v.abundances;
+  }
+  if (bad.load()) { set_err(errbuf, errlen, "dada2hip: a derep object holds an empty sequence or a negative abundance."); return DADA2HIP_ERR_INPUT; }
+  lap(0);
+  PoolPlan P;
+  int32_t bs = 0, bj = 0;
+  const int prc = pool_group(nsamples, S.data(), P, &bs, &bj);
+  lap(1);
+  if (prc == POOL_DUPLICATE) {
+    set_err(errbuf, errlen, ("dada2hip: derep object " + std::to_string(bs + 1) + " holds the sequence of its unique " + std::to_string(bj + 1) + " twice.").c_str());
+    return DADA2HIP_ERR_INPUT;
+  }
+  if (prc == POOL_OVERFLOW) {
+    set_err(errbuf, errlen, "dada2hip: a pooled abundance exceeds the integer range (R: NAs produced by integer overflow).");
+    return DADA2HIP_ERR_INPUT;
+  }
+  pool_order(P, [](int32_t *f, size_t n, auto less) { pool_sort(f, n, less); });
+  lap(2);
+  const size_t U = (size_t)P.npool, ml = (size_t)maxlen;
+  std::unique_ptr<dada2hip_derep> d(new dada2hip_derep());
+  d->nreads = nreads; d->maxlen = maxlen;
+  d->abund.resize(U); d->seq_ptrs.resize(U);
+  std::vector<size_t> soff(U + 1, 0);
+  for (size_t k = 0; k < U; k++) soff[k + 1] = soff[k] + S[P.src_sample[P.order[k]]].len[P.src_index[P.order[k]]] + 1;
+  d->seq_blob.reset(new char[std::max<size_t>(soff[U], 1)]);
+  d->quals.reset(new double[std::max<size_t>(U * ml, 1)]);
+  const double na = na_real();
+  d2::parallel_for(U, 128, [&](size_t k0, size_t k1) {
+    for (size_t k = k0; k < k1; k++) {
+      const int32_t p = P.order[k];
+      const PoolSample &A = S[P.src_sample[p]];
+      const size_t n = A.len[P.src_index[p]];
+      char *dst = d->seq_blob.get() + soff[k];
+      memcpy(dst, A.seqs[P.src_index[p]], n);
+      dst[n] = 0;
+      d->seq_ptrs[k] = dst;
+      d->abund[k] = (int32_t)P.total[p];
+      double *row = &d->quals[k * ml];
+      size_t lim = std::min(n, ml);                            // positions every contributing sample has a column for
+      for (int64_t c = P.contrib_off[p]; c < P.contrib_off[p + 1]; c++) lim = std::min(lim, (size_t)in[P.contrib_sample[c]].maxlen);
+      for (size_t x = 0; x < lim; x++) row[x] = 0.0;
+      for (int64_t c = P.contrib_off[p]; c < P.contrib_off[p + 1]; c++) {
+        const dada2hip_derep_view &v = in[P.contrib_sample[c]];
+        const double *q = v.quals + (size_t)P.contrib_index[c] * (size_t)v.maxlen;
+        const double cnt = (double)v.abundances[P.contrib_index[c]];
+        for (size_t x = 0; x < lim; x++) {
+          const double prod = q[x] * cnt;                       // (two roundings: see above)
+          row[x] = row[x] + prod;
+        }
+      }
+      const double tot = (double)P.total[p];
+      for (size_t x = 0; x < lim; x++) row[x] = row[x] / tot;
+      for (size_t x = lim; x < ml; x++) row[x] = na;
+    }
+  });
+  lap(3);
+  // the maps one after the other, through each sample's piece of to_pool
+  d->map.resize((size_t)nreads);
+  size_t at = 0;
+  std::atomic<int> bad_map{0};
+  for (int32_t s = 0; s < nsamples; s++) {
+    const dada2hip_derep_view &v = in[s];
+    const int32_t *tp = P.to_pool.data() + first[s];
+    int32_t *o = d->map.data() + at;
+    d2::parallel_for((size_t)v.nreads, 65536, [&](size_t i0, size_t i1) {
+      for (size_t i = i0; i < i1; i++)
+        if (!pool_map_entry(v.map[i], tp, v.nuniques, DADA2HIP_NA_INTEGER, &o[i])) bad_map.store(1, std::memory_order_relaxed);
+    });
+    at += (size_t)v.nreads;
+  }
+  if (bad_map.load()) { set_err(errbuf, errlen, "dada2hip: a derep object's map names a unique it does not hold."); return DADA2HIP_ERR_INPUT; }
+  if (unique_to_pool && nall) memcpy(unique_to_pool, P.to_pool.data(), nall * sizeof(int32_t));
+  lap(4);
+  if (d2::knobs().derep_times)
+    fprintf(stderr, "[combine] %d samples, %zu uniques -> %zu: lengths + hashes %.0f ms, union %.0f ms, order %.0f ms, sequences + quality rows %.0f ms, maps %.0f ms\n",
+            (int)nsamples, nall, U, ms_phase[0], ms_phase[1], ms_phase[2], ms_phase[3], ms_phase[4]);
+  *out = d.release();
+  return DADA2HIP_OK;
+}
+
+}  // namespace
+
+extern "C" int dada2hip_derep_combine(int32_t nsamples, const dada2hip_derep_view *in, dada2hip_derep **out, int32_t *unique_to_pool,
+                                      char *errbuf, size_t errlen) {
+  try {
+    return derep_combine_body(nsamples, in, out, unique_to_pool, errbuf, errlen);
+  } catch (const std::bad_alloc &) {
+    set_err(errbuf, errlen, "dada2hip: out of host memory while combining derep objects");
+  } catch (const std::exception &e) {
+    set_err(errbuf, errlen, (std::string("dada2hip: ") + e.what()).c_str());
+  } catch (...) {
+    set_err(errbuf, errlen, "dada2hip: unknown error while combining derep objects");
+  }
+  if (out) *out = nullptr;
+  return DADA2HIP_ERR_RUNTIME;
+}
+
 // ---- filterAndTrim's file level (R/filter.R:613-730 fastqFilter, :878-1140 fastqPairedFilter) -------------------------------------
 // The per-read verdicts are dada2hip_filter_reads' (filter_host.h, filter.inc.hip); here are the reader, the chunks, the paired
 // AND and the writer.  A chunk's records are copied out of the reader's lines into three blobs (header lines, sequences,

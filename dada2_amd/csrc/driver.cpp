@@ -103,6 +103,7 @@ struct dada2hip_sample {
   std::vector<int32_t> h_len;
   std::vector<uint32_t> h_reads;
   std::vector<uint8_t> h_prior;
+  int64_t prior_seqs_stats[DADA2HIP_PRIOR_SEQS_NSTATS] = {0};   // of the last dada2hip_sample_set_prior_seqs (priors_host.h)
   uint64_t total_reads = 0;
   int qmax = 0;
   double ms_upload = 0;
@@ -3584,6 +3585,9 @@ extern "C++" {
 
 // ---- removePrimers: primer search on both strands, orientation and the kept window (R/filter.R:81-233) ----
 #include "primers_host.h"
+
+// ---- priors by sequence on a resident sample: names(uniques) %in% c(priors, pseudo_priors) (R/dada.R:335) ----
+#include "priors_host.h"
 
 // ---- result getters ------------------------------------------------------------------------------
 int32_t dada2hip_result_nclust(const dada2hip_result *r) { return r->nclust; }

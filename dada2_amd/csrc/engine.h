@@ -674,6 +674,20 @@ struct PrimerOut { int32_t code, flip, first, last, hits[4]; };
 // starts (optional): [r * 8 + 2 k], [+ 1] the first and the last start of pattern k, 1-based on the strand it stands for
 void launch_primers(const PrimerArgs &A, int n, const uint8_t *d_seq, const long long *d_off, PrimerOut *d_out, int32_t *d_starts,
                     hipStream_t st);
+// priors by sequence (priors.inc.hip).  The prior sequences are packed like a sample's uniques; keys / groups as in SpeciesKeys (the
+// distinct prefix keys - the first min(32, length) bases -, ascending inside each key length's group; groups[g] = {key length, first
+// key, number of keys}).  The rows lie key by key: those of key k are rows key_row_off[k] .. key_row_off[k + 1], in the caller's
+// order; row r is row_len[r] bases from word row_woff[r] (a multiple of 4) of row_words and is the caller's entry row_seq[r].
+struct PriorKeys {
+  const unsigned long long *keys;
+  const int32_t *groups;
+  int ngroups, nkeys;
+  const int32_t *key_row_off, *row_woff, *row_len, *row_seq;
+  const uint32_t *row_words;
+};
+constexpr int PRIOR_LDS_KEYS_MAX = 6144;      // 48 KiB of keys per block
+int launch_prior_match(const SampleDev &S, const PriorKeys &K, bool lds, int grid_cap, const uint8_t *d_or_flags, int32_t *d_first_match,
+                       hipStream_t st);
 void launch_calc_pA(int n, const int32_t *d_reads, const double *d_E, const uint8_t *d_prior, double *d_out,
                     hipStream_t st);
 

@@ -78,8 +78,10 @@ struct Knobs {
   long long primers_tile = 0;         // DADA2HIP_PRIMERS_TILE=n        ... chunks of 64 match starts per tile of a read (at least 1; at most, and unset, 64)
   int species_cand = 1 << 20;         // DADA2HIP_SPECIES_CAND=n        assignSpecies: records of the candidate buffer and of the hit buffer (a launch that counts more is re-run in pieces)
   int species_chunk = 8192;           // DADA2HIP_SPECIES_CHUNK=n       ... distinct queries per pass over the references (at most 8 192: the presence bitmap is sized for it)
+  int priors_lds_keys = 4096;         // DADA2HIP_PRIORS_LDS_KEYS=n     priors by sequence: up to n distinct prefix keys are searched in LDS, more in global memory (at most 6 144; 0 = always global; tests: the global path on a small set)
+  int priors_grid = 0;                // DADA2HIP_PRIORS_GRID=n         ... block cap of k_prior_match (0 = 2048; tests: blocks that stride on a small sample)
   bool derep_zlib = false;           // DADA2HIP_DEREP_INFLATE=zlib    .gz files through zlib's streaming inflate even where libdeflate is installed
-  bool derep_times = false;           // DADA2HIP_DEREP_TIMES=1         stderr: phases of a dada2hip_derep_fastq call
+  bool derep_times = false;           // DADA2HIP_DEREP_TIMES=1         stderr: phases of a dada2hip_derep_fastq / dada2hip_derep_combine call
   // (read once per process, when the host pool / the allocation cache are created: DADA2HIP_HOST_THREADS, DADA2HIP_ALLOC_CACHE,
   //  DADA2HIP_ALLOC_CACHE_GB)
   int host_threads = 0;
@@ -139,6 +141,7 @@ struct Knobs {
     k.nw_ring = P("DADA2HIP_NW_RING");
     k.primers_piece = P("DADA2HIP_PRIMERS_PIECE"); k.primers_piece_bytes = P("DADA2HIP_PRIMERS_PIECE_BYTES"); k.primers_tile = P("DADA2HIP_PRIMERS_TILE");
     k.species_cand = I("DADA2HIP_SPECIES_CAND", 1 << 20); k.species_chunk = I("DADA2HIP_SPECIES_CHUNK", 8192);
+    k.priors_lds_keys = I("DADA2HIP_PRIORS_LDS_KEYS", 4096); k.priors_grid = I("DADA2HIP_PRIORS_GRID", 0);
     if (const char *e = S("DADA2HIP_DEREP_INFLATE")) k.derep_zlib = !std::strcmp(e, "zlib");
     if (const char *e = S("DADA2HIP_DEREP_TIMES")) k.derep_times = !std::strcmp(e, "1");
     k.host_threads = I("DADA2HIP_HOST_THREADS", 0);

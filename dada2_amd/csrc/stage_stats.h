@@ -16,6 +16,8 @@ enum { FS_IN = 0, FS_KEPT, FS_STAGE1, FS_KEYS = 13, FS_LDS, FS_BYTES, FS_US_UP, 
        FS_US_DEFLATE, FS_US_WRITE, FS_US_TOTAL, FS_US_INFLATE, FS_COUNT };
 enum { PS_IN = 0, PS_KEPT, PS_CODE1, PS_FLIPPED = 6, PS_MULTI, PS_HITS_FWD, PS_HITS_REV, PS_PIECES, PS_TILES, PS_BYTES, PS_US_UP, PS_US_KERNEL,
        PS_US_DOWN, PS_US_PARSE, PS_US_DEFLATE, PS_US_WRITE, PS_US_TOTAL, PS_US_INFLATE, PS_COUNT };
+enum { QS_GIVEN = 0, QS_KEPT, QS_KEYS, QS_LDS, QS_SET, QS_BLOCKS, QS_US_PACK, QS_US_DEVICE, QS_US_KERNEL, QS_US_TOTAL, QS_COUNT };   // dada2hip_sample_set_prior_seqs
+static_assert(QS_COUNT <= DADA2HIP_PRIOR_SEQS_NSTATS, "stats words");
 // How a file adds its chunks' calls up.  Filter: the words of the context are taken, the call's total is the file's own, every other
 // word adds; of a pair's second file only the bytes and the call's clocks add.  Primers: every word of the call adds.
 enum { FS_TAKEN_FIRST = FS_KEYS, FS_TAKEN_LAST = FS_LDS, FS_CLOCK_FIRST = FS_BYTES, FS_CLOCK_LAST = FS_US_DOWN, PS_CALL_LAST = PS_US_DOWN };

@@ -195,3 +195,18 @@ def make_sample(err: np.ndarray, n_uniques: int, L: int = 250, G: int = 256, see
     if d.quals.shape[1] != maxlen:
         d = Derep(d.seqs, d.abundances, np.ascontiguousarray(d.quals[:, :maxlen]), d.map)
     return d
+
+
+def make_shared_truth_samples(err: np.ndarray, n_uniques: int = 250_000, nsamples: int = 8, L: int = 250, G: int = 512,
+                              seed: int = 20260929, **kw) -> list:
+    """``nsamples`` samples that share half of their true variants (BASELINE.json configs[3]: 8 x 250 000 uniques x 250 nt, G = 512;
+    the defaults, seed included, draw the samples bench.py's config 4 draws).  The other half of a sample's variants are its own,
+    and the abundance ranks of the variants differ per sample."""
+    shared = true_variants(np.random.default_rng(seed), G // 2, L)
+    out = []
+    for i in range(nsamples):
+        own = true_variants(np.random.default_rng(seed + 17 * (i + 1)), G - G // 2, L)
+        tv, tl = np.concatenate([shared[0], own[0]]), np.concatenate([shared[1], own[1]])
+        perm = np.random.default_rng(99 + i).permutation(tv.shape[0])
+        out.append(make_sample(err, n_uniques, L=L, G=G, seed=seed + 1000 * (i + 1), variants=(tv[perm], tl[perm]), **kw))
+    return out

@@ -22,6 +22,8 @@
  *   dada2hip_taxonomy_*     <- C_assign_taxonomy2() src/taxonomy.cpp:206-338  (`_dada2_C_assign_taxonomy2`; R/taxonomy.R:135), split into
  *                              the model (:219-270, built once, resident in HBM) and the classification of queries (:113-200)
  *   dada2hip_derep_*        <- derepFastq() / qtables2()  R/sequenceIO.R:45-124, :150-183 (host-side C++, zlib)
+ *   dada2hip_derep_combine  <- combineDereps2()    R/multiSample.R:165-203 (dada(pool = TRUE), R/dada.R:189-192; host-side C++)
+ *   dada2hip_sample_set_prior_seqs <- names(uniques) %in% c(priors, pseudo_priors)  R/dada.R:335, on the resident uniques
  *   dada2hip_filter_*       <- filterAndTrim() / fastqFilter() / fastqPairedFilter() / isPhiX() / seqComplexity()  R/filter.R:402-1275 on
  *                              C_matchRef / C_matrixEE (src/filter.cpp:7-49)
  *   dada2hip_primers_*      <- removePrimers()  R/filter.R:81-233 (vmatchPattern without indels, restated)
@@ -64,6 +66,8 @@
  *   DADA2HIP_PRIMERS_PIECE=<n>         dada2hip_primers_reads: reads per piece of a call (at least 1; default and at most 65 536)
  *   DADA2HIP_PRIMERS_PIECE_BYTES=<n>   ... bases per piece (at least 1; default and at most 32 MiB; a longer read is a piece of its own)
  *   DADA2HIP_PRIMERS_TILE=<n>          ... chunks of 64 match starts per tile of a read (at least 1; default and at most 64)
+ *   DADA2HIP_PRIORS_LDS_KEYS=<n>       dada2hip_sample_set_prior_seqs: up to n distinct prefix keys are searched in LDS, more in global
+ *                                      memory (default 4 096, at most 6 144; 0 = always global memory)
  *   DADA2HIP_PROFILE=1, DADA2HIP_V2_SUMMARY, DADA2HIP_V2_DEBUG   per-launch device times in the stats; traces on stderr
  * Test / tuning knobs (sizes of rings and grids, forced growth paths, injected failures) are listed with their meaning in
  * knobs.h and DESIGN.md §10b; they are not part of the interface.
@@ -216,6 +220,19 @@ int dada2hip_sample_create(int32_t nraw, const char *const *seqs, const int32_t 
                            const uint8_t *priors, const double *quals, int32_t quals_nrow, int32_t device,
                            dada2hip_sample **out, char *errbuf, size_t errlen);
 int dada2hip_sample_set_priors(dada2hip_sample *s, const uint8_t *priors, char *errbuf, size_t errlen);
+/* Priors given as SEQUENCES - names(uniques) %in% c(priors, pseudo_priors), R/dada.R:335 - matched on the device against the resident
+ * uniques: the flag of unique i becomes (or_flags ? or_flags[i] != 0 : 0) | (its sequence is one of seqs).  Entries of seqs with a
+ * letter outside upper-case A/C/G/T, or empty, match nothing and are no error (%in% does not mind them); duplicates are allowed.
+ * first_match (optional, N entries): R's match(uniques, seqs) - 1, the SMALLEST index of an equal entry, -1 for none.  nset
+ * (optional): the flags set after the call.  n == 0 clears the flags, or leaves exactly or_flags.  A sharded sample flags all N
+ * uniques, as dada2hip_sample_set_priors does.  dada2hip_sample_prior_seqs_stats: the words of the sample's LAST such call
+ * (DADA2HIP_PRIOR_SEQS_NSTATS int64): [0] entries given, [1] entries kept, [2] distinct prefix keys, [3] 1 = the keys were staged in
+ * LDS (DADA2HIP_PRIORS_LDS_KEYS), [4] flags set, [5] blocks launched, [6] host packing and tables, [7] the host's wall time from the first upload to the end of the
+ * copy back (the kernel inside it), [8] the kernel by device events (DADA2HIP_PROFILE=1 only), [9] the whole call; [6]-[9] microseconds. */
+#define DADA2HIP_PRIOR_SEQS_NSTATS 16
+int dada2hip_sample_set_prior_seqs(dada2hip_sample *s, int32_t n, const char *const *seqs, const uint8_t *or_flags,
+                                   int32_t *first_match, int32_t *nset, char *errbuf, size_t errlen);
+void dada2hip_sample_prior_seqs_stats(const dada2hip_sample *s, int64_t *stats);
 int dada2hip_sample_run(dada2hip_sample *s, const double *err, int32_t err_ncol, const dada2hip_opts *opts,
                         const dada2hip_hooks *hooks, dada2hip_result **out, char *errbuf, size_t errlen);
 void dada2hip_sample_free(dada2hip_sample *s);
@@ -348,6 +365,30 @@ const int32_t *dada2hip_derep_map(const dada2hip_derep *d);
 void dada2hip_derep_free(dada2hip_derep *d);
 int dada2hip_sample_from_derep(const dada2hip_derep *d, const uint8_t *priors, int32_t device, dada2hip_sample **out,
                                char *errbuf, size_t errlen);
+
+/* ---- pooling: the samples' derep objects into one (combineDereps2, R/multiSample.R:165-203; dada(pool = TRUE), R/dada.R:189-192) ----
+ * A view is one sample as the accessors above expose it, or as the caller holds it.  dada2hip_derep_combine returns an ordinary
+ * dada2hip_derep - every accessor above and dada2hip_sample_from_derep take it - that equals combineDereps2 field for field:
+ *   seqs        the union of the samples' uniques: order of first appearance over the samples as given, each sample's uniques in
+ *               their own order, then ordered by decreasing summed abundance, stably (R's order(decreasing = TRUE))
+ *   abundances  int32 sums; a sum past INT32_MAX is DADA2HIP_ERR_INPUT (R: NA and a warning)
+ *   quals       per pooled unique and position acc = 0.0; acc = acc + q * (double)abundance for each contributing sample in sample
+ *               order - a multiply and an add, each rounded, never fused -; acc / (double)sum.  NA past the unique's length and past
+ *               the maxlen of a contributing sample that is narrower (the cbind(..., NA) of :184); maxlen is the widest sample's
+ *   map         the samples' maps one after the other, renumbered to the pooled rows; DADA2HIP_NA_INTEGER stays
+ * unique_to_pool (optional; sum of nuniques entries, sample after sample): the 0-based pooled row of every unique of every sample -
+ * what the split of a pooled result back into samples needs (R/dada.R:454, :467).  A sample that holds one sequence twice, an empty
+ * sequence, a negative abundance or a map entry that names no unique is DADA2HIP_ERR_INPUT.  Host-side: no device is touched. */
+typedef struct dada2hip_derep_view {
+  int32_t nuniques, maxlen;
+  int64_t nreads;
+  const char *const *seqs;
+  const int32_t *abundances;
+  const double *quals;           /* nuniques rows of maxlen doubles, NA past a unique's length */
+  const int32_t *map;            /* nreads entries, 0-based, DADA2HIP_NA_INTEGER allowed; may be NULL when nreads == 0 */
+} dada2hip_derep_view;
+int dada2hip_derep_combine(int32_t nsamples, const dada2hip_derep_view *in, dada2hip_derep **out, int32_t *unique_to_pool,
+                           char *errbuf, size_t errlen);
 
 /* ---- mergePairs: denoised forward + reverse reads -> merged amplicons -------------------------
  * dada2hip_merge_pairs == the per-sample body of mergePairs(dadaF, derepF, dadaR, derepR, minOverlap, maxMismatch,
