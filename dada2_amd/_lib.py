@@ -126,6 +126,9 @@ EXPORTS = [
     "dada2hip_filter_open", "dada2hip_filter_free", "dada2hip_filter_reads", "dada2hip_filter_fastq", "dada2hip_filter_fastq_paired",
     "dada2hip_primers_reads", "dada2hip_primers_fastq",
     "dada2hip_derep_combine", "dada2hip_sample_set_prior_seqs", "dada2hip_sample_prior_seqs_stats",
+    "dada2hip_qprofile_reads", "dada2hip_qprofile_fastq", "dada2hip_qprofile_ncycle", "dada2hip_qprofile_counts",
+    "dada2hip_qprofile_reads_total", "dada2hip_qprofile_profiled", "dada2hip_qprofile_qual_offset", "dada2hip_qprofile_free",
+    "dada2hip_complexity_reads", "dada2hip_complexity_fastq", "dada2hip_complexity_free",
 ]
 
 PRIOR_SEQS_NSTATS = 16   # DADA2HIP_PRIOR_SEQS_NSTATS
@@ -184,6 +187,13 @@ class CPrimerParams(C.Structure):
     """dada2hip_primer_params"""
     _fields_ = [("primer_fwd", C.c_char_p), ("primer_rev", C.c_char_p), ("max_mismatch", C.c_int32), ("trim_fwd", C.c_int32),
                 ("trim_rev", C.c_int32), ("orient", C.c_int32), ("allow_indels", C.c_int32), ("reserved", C.c_int32)]
+
+
+READQC_NSTATS = 16   # DADA2HIP_READQC_NSTATS
+QPROFILE_NSCORE = 94   # DADA2HIP_QPROFILE_NSCORE: the quality letters '!' .. '~'
+# the int64 words of the stats of dada2hip_qprofile_* / dada2hip_complexity_*, in order
+READQC_STATS = ("reads_in", "reads_profiled", "pieces", "cycles", "upload_bytes", "upload_us", "kernel_device_us", "download_us", "parse_us",
+                "total_us", "open_inflate_us")
 
 
 class CSampleInput(C.Structure):
@@ -356,6 +366,19 @@ def lib():
     L.dada2hip_sample_set_prior_seqs.argtypes = [vp, ip, vp, vp, vp, C.POINTER(ip), cp, C.c_size_t]
     L.dada2hip_sample_prior_seqs_stats.argtypes = [vp, vp]
     L.dada2hip_sample_prior_seqs_stats.restype = None
+    i64 = C.c_int64
+    L.dada2hip_qprofile_reads.argtypes = [i64, vp, vp, ip, ip, vp, vp, cp, C.c_size_t]
+    L.dada2hip_qprofile_fastq.argtypes = [cp, i64, i64, ip, ip, C.POINTER(vp), vp, cp, C.c_size_t]
+    for name, rt in (("ncycle", ip), ("counts", C.POINTER(i64)), ("reads_total", i64), ("profiled", i64), ("qual_offset", ip)):
+        f = getattr(L, "dada2hip_qprofile_" + name)
+        f.argtypes = [vp]
+        f.restype = rt
+    L.dada2hip_qprofile_free.argtypes = [vp]
+    L.dada2hip_qprofile_free.restype = None
+    L.dada2hip_complexity_reads.argtypes = [i64, vp, vp, ip, ip, ip, ip, vp, vp, cp, C.c_size_t]
+    L.dada2hip_complexity_fastq.argtypes = [cp, i64, i64, ip, ip, ip, ip, C.POINTER(vp), C.POINTER(i64), vp, cp, C.c_size_t]
+    L.dada2hip_complexity_free.argtypes = [vp]
+    L.dada2hip_complexity_free.restype = None
     L.dada2hip_trim_cache.argtypes = []
     L.dada2hip_trim_cache.restype = None
     _lib = L

@@ -733,7 +733,17 @@ extern "C" int dada2hip_derep_combine(int32_t nsamples, const dada2hip_derep_vie
 // qualities) and the offsets the kernels take; the kept records are laid out as ShortRead's writeFastq does (`@id`, the bases, a
 // bare `+`, the qualities) by the host pool and, with compress, deflated in pieces over the pool, every piece a gzip member of
 // its own (concatenated members are one valid .gz; a single deflate stream on one thread would be the whole run).
+#include <sys/stat.h>
+
+#include "readqc_plain.h"
 #include "stage_stats.h"
+
+// the per-cycle quality table of a file (dada2hip_qprofile_fastq): counts[cycle * 94 + letter - '!']
+struct dada2hip_qprofile {
+  int32_t ncycle = 0, qual_offset = 0;
+  int64_t reads = 0, profiled = 0;
+  std::vector<int64_t> counts;
+};
 
 namespace {
 
@@ -922,6 +932,8 @@ struct FqCall {
 // verdict(ch, first_chunk, keep, win, flip) settles a chunk: keep[i] (set to 1 on entry), win[k] (offset and length per read of
 // file k) and, for reads to be written as their reverse complement, flip (empty: none); it returns a DADA2HIP_* code with the
 // message in errbuf.  On any failure nothing half written is left behind.  W: where the pipeline's clocks go in `tot`.
+// out == nullptr is the form without writers (the read diagnostics): nothing is removed, nothing written, and W.deflate and
+// W.write are not looked at; the verdict only reads the chunk.
 struct FqClockWords { int parse, deflate, write, inflate; };
 template <typename Verdict>
 int fq_run_chunks(int nfile, const char *const *in, const char *const *out, int32_t compress, int64_t chunk_reads, int64_t *tot,
@@ -937,9 +949,9 @@ int fq_run_chunks(int nfile, const char *const *in, const char *const *out, int3
     const auto t_open = fclk::now();                            // (a .gz that libdeflate takes is inflated HERE, in one go)
     if (!src[k].open(in[k], err)) { set_err(errbuf, errlen, err.c_str()); return DADA2HIP_ERR_INPUT; }
     tot[W.inflate] += us_since(t_open);
-    wr[k].path = out[k]; wr[k].compress = compress != 0;
+    if (out) { wr[k].path = out[k]; wr[k].compress = compress != 0; }
   }
-  for (int k = 0; k < nfile; k++) (void)remove(out[k]);         // :634-640 (writeFastq does not overwrite)
+  for (int k = 0; k < nfile && out; k++) (void)remove(out[k]);  // :634-640 (writeFastq does not overwrite)
   std::vector<int32_t> win[2];
   std::vector<uint8_t> keep, flip;
   int rc = DADA2HIP_OK;
@@ -972,17 +984,17 @@ int fq_run_chunks(int nfile, const char *const *in, const char *const *out, int3
     rc = verdict(ch, first, keep, win, flip);
     if (rc != DADA2HIP_OK) break;
     for (int64_t i = 0; i < n; i++) nout += keep[i];
-    for (int k = 0; k < nfile && rc == DADA2HIP_OK; k++)
+    for (int k = 0; k < nfile && out && rc == DADA2HIP_OK; k++)
       if (!wr[k].put(ch[k], keep, win[k], flip, err)) { set_err(errbuf, errlen, err.c_str()); rc = DADA2HIP_ERR_RUNTIME; }
     if (rc != DADA2HIP_OK) break;
   }
   if (ahead.valid()) ahead.wait();                              // (a run that stops early still waits for its parser)
-  for (int k = 0; k < nfile; k++) {
+  for (int k = 0; k < nfile && out; k++) {
     if (!wr[k].finish(err) && rc == DADA2HIP_OK) { set_err(errbuf, errlen, err.c_str()); rc = DADA2HIP_ERR_RUNTIME; }
     tot[W.deflate] += wr[k].us_deflate; tot[W.write] += wr[k].us_write;
   }
   if (rc != DADA2HIP_OK)                                        // nothing half written is left behind
-    for (int k = 0; k < nfile; k++) (void)remove(out[k]);
+    for (int k = 0; k < nfile && out; k++) (void)remove(out[k]);
   return rc;
 }
 
@@ -1069,6 +1081,114 @@ int primers_file_body(const char *in, const char *out, const dada2hip_primer_par
   return call.finish(tot, sizeof tot, PS_US_TOTAL, stats);
 }
 
+// ---- the read diagnostics' file level (R/plot-methods.R:163-243 on qa()'s perCycle$quality; :293-299 plotComplexity) ----------------
+// fq_run_chunks without writers: a chunk's first records, while fewer than max_reads have been profiled (0: no limit), go to
+// dada2hip_qprofile_reads / the complexity calls; the rest of the file is still parsed, for its count of records.
+inline int64_t rq_take(const FqChunk &c, int64_t max_reads, int64_t done) { return max_reads > 0 ? std::max<int64_t>(0, std::min(c.n, max_reads - done)) : c.n; }
+inline bool rq_is_dir(const char *path) { struct stat sb; return stat(path, &sb) == 0 && S_ISDIR(sb.st_mode); }
+inline void rq_add_call(int64_t *tot, const int64_t *st) {
+  for (int i = RQ_CALL_FIRST; i <= RQ_CALL_LAST; i++)
+    if (i == RQ_CYCLES) tot[i] = std::max(tot[i], st[i]); else tot[i] += st[i];
+}
+
+int qprofile_file_body(const char *path, int64_t chunk_reads, int64_t max_reads, int32_t qual_offset, int32_t device, dada2hip_qprofile **out,
+                       int64_t *stats, char *errbuf, size_t errlen) {
+  FqCall call(nullptr, nullptr);
+  if (out) *out = nullptr;
+  if (!path || !out) { set_err(errbuf, errlen, "File paths must be provided in character format."); return DADA2HIP_ERR_INPUT; }
+  if (max_reads < 0 || (qual_offset != 0 && qual_offset != 33 && qual_offset != 64)) {
+    set_err(errbuf, errlen, "dada2hip: the quality offset must be 33, 64 or 0 (Auto), and the number of reads profiled not negative.");
+    return DADA2HIP_ERR_INPUT;
+  }
+  if (rq_is_dir(path)) { set_err(errbuf, errlen, "dada2hip: a directory is not profiled; name its files."); return DADA2HIP_ERR_INPUT; }
+  std::unique_ptr<dada2hip_qprofile> P(new dada2hip_qprofile());
+  P->qual_offset = qual_offset;
+  int64_t tot[DADA2HIP_READQC_NSTATS] = {0}, st[DADA2HIP_READQC_NSTATS];
+  std::vector<int64_t> piece;
+  const int rc = fq_run_chunks(1, &path, nullptr, 0, chunk_reads, tot, FqClockWords{RQ_US_PARSE, RQ_US_PARSE, RQ_US_PARSE, RQ_US_INFLATE}, call,
+                               [&](FqChunk *ch, bool first, std::vector<uint8_t> &, std::vector<int32_t> *, std::vector<uint8_t> &) -> int {
+    const FqChunk &c = ch[0];
+    if (first && P->qual_offset == 0) P->qual_offset = fq_auto_offset(c);
+    const int64_t take = rq_take(c, max_reads, P->profiled);
+    if (take <= 0) return DADA2HIP_OK;
+    int64_t mx = 0;
+    for (int64_t i = 0; i < take; i++) mx = std::max(mx, c.off[i + 1] - c.off[i]);
+    if (mx > (int64_t)1 << 18) {
+      set_err(errbuf, errlen, "dada2hip: a read of more than 262144 cycles is not supported by the quality profile.");
+      return DADA2HIP_ERR_UNSUPPORTED;
+    }
+    if (mx > P->ncycle) { P->counts.resize((size_t)mx * DADA2HIP_QPROFILE_NSCORE, 0); P->ncycle = (int32_t)mx; }   // a later chunk with a longer read
+    piece.resize((size_t)mx * DADA2HIP_QPROFILE_NSCORE);
+    const int r = dada2hip_qprofile_reads(take, c.qual.empty() ? "" : c.qual.data(), c.off.data(), device, (int32_t)mx, piece.data(), st, errbuf, errlen);
+    if (r != DADA2HIP_OK) {
+      if (r == DADA2HIP_ERR_INPUT)                              // a letter outside '!'..'~': name the record, not its number in the chunk
+        for (int64_t i = 0; i < c.off[take]; i++) {
+          const unsigned char q = (unsigned char)c.qual[(size_t)i];
+          if (q >= 33 && q <= 126) continue;
+          const int64_t rd = std::upper_bound(c.off.begin(), c.off.end(), i) - c.off.begin() - 1;
+          const std::string id(c.hdr.data() + c.hoff[rd], (size_t)(c.hoff[rd + 1] - c.hoff[rd]));
+          set_err(errbuf, errlen, ("dada2hip: read " + std::to_string(call.nin - c.n + rd + 1) + " (" + id + ") holds a quality letter outside '!'..'~'.").c_str());
+          break;
+        }
+      return r;
+    }
+    for (size_t i = 0; i < piece.size(); i++) P->counts[i] += piece[i];
+    rq_add_call(tot, st);
+    P->profiled += take;
+    return DADA2HIP_OK;
+  }, errbuf, errlen);
+  if (rc != DADA2HIP_OK) return rc;
+  if (P->qual_offset == 0) P->qual_offset = 33;
+  P->reads = call.nin;
+  call.nout = P->profiled;
+  *out = P.release();
+  return call.finish(tot, sizeof tot, RQ_US_TOTAL, stats);
+}
+
+int complexity_file_body(const char *path, int64_t chunk_reads, int64_t max_reads, int32_t kmer_size, int32_t window, int32_t by, int32_t device,
+                         double **out, int64_t *nout, int64_t *stats, char *errbuf, size_t errlen) {
+  FqCall call(nullptr, nullptr);
+  if (out) *out = nullptr;
+  if (nout) *nout = 0;
+  if (!path || !out || !nout) { set_err(errbuf, errlen, "File paths must be provided in character format."); return DADA2HIP_ERR_INPUT; }
+  if (max_reads < 0) { set_err(errbuf, errlen, "dada2hip: the number of reads profiled must not be negative."); return DADA2HIP_ERR_INPUT; }
+  if (rq_is_dir(path)) { set_err(errbuf, errlen, "dada2hip: a directory is not profiled; name its files."); return DADA2HIP_ERR_INPUT; }
+  // (the refusals of the arguments, before the file is touched: a call on no reads makes them)
+  int r0 = window == 0 ? dada2hip_complexity_reads(0, nullptr, nullptr, kmer_size, 0, by, device, nullptr, nullptr, errbuf, errlen)
+                       : d2_complexity_pairs(0, nullptr, nullptr, kmer_size, window, by, device, nullptr, nullptr, errbuf, errlen);
+  if (r0 != DADA2HIP_OK) return r0;
+  const int k = kmer_size == 0 ? 2 : kmer_size;
+  int64_t tot[DADA2HIP_READQC_NSTATS] = {0}, st[DADA2HIP_READQC_NSTATS];
+  std::vector<double> vals;                                     // window 0: the values; otherwise the pairs of readqc_plain.h
+  std::vector<int64_t> lens;
+  int64_t done = 0, maxlen = 0;
+  const int rc = fq_run_chunks(1, &path, nullptr, 0, chunk_reads, tot, FqClockWords{RQ_US_PARSE, RQ_US_PARSE, RQ_US_PARSE, RQ_US_INFLATE}, call,
+                               [&](FqChunk *ch, bool, std::vector<uint8_t> &, std::vector<int32_t> *, std::vector<uint8_t> &) -> int {
+    const FqChunk &c = ch[0];
+    const int64_t take = rq_take(c, max_reads, done);
+    if (take <= 0) return DADA2HIP_OK;
+    const char *seq = c.seq.empty() ? "" : c.seq.data();
+    const size_t per = window == 0 ? 1 : 2, at = vals.size();
+    vals.resize(at + per * (size_t)take);
+    const int r = window == 0 ? dada2hip_complexity_reads(take, seq, c.off.data(), kmer_size, 0, by, device, vals.data() + at, st, errbuf, errlen)
+                              : d2_complexity_pairs(take, seq, c.off.data(), kmer_size, window, by, device, vals.data() + at, st, errbuf, errlen);
+    if (r != DADA2HIP_OK) return r;
+    for (int64_t i = 0; i < take; i++) { lens.push_back(c.off[i + 1] - c.off[i]); maxlen = std::max(maxlen, lens.back()); }
+    rq_add_call(tot, st);
+    done += take;
+    return DADA2HIP_OK;
+  }, errbuf, errlen);
+  if (rc != DADA2HIP_OK) return rc;
+  if (window > 0 && maxlen - window < 1) { set_err(errbuf, errlen, CW_ERR_NO_START); return DADA2HIP_ERR_INPUT; }
+  double *res = (double *)malloc(std::max<size_t>(1, (size_t)done) * sizeof(double));
+  if (!res) throw std::bad_alloc();
+  for (int64_t i = 0; i < done; i++)
+    res[i] = window == 0 ? vals[(size_t)i] : cw_finish(lens[(size_t)i], maxlen, vals[2 * (size_t)i], vals[2 * (size_t)i + 1], k);
+  *out = res; *nout = done;
+  call.nout = done;
+  return call.finish(tot, sizeof tot, RQ_US_TOTAL, stats);
+}
+
 template <typename F> int filter_files_guarded(char *errbuf, size_t errlen, F &&f) {
   try {
     return f();
@@ -1109,5 +1229,26 @@ int dada2hip_primers_fastq(const char *in, const char *out, const dada2hip_prime
     return primers_file_body(in, out, params, compress, chunk_reads, device, reads_in, reads_out, stats, errbuf, errlen);
   });
 }
+
+int dada2hip_qprofile_fastq(const char *path, int64_t chunk_reads, int64_t max_reads, int32_t qual_offset, int32_t device,
+                            dada2hip_qprofile **out, int64_t *stats, char *errbuf, size_t errlen) {
+  return filter_files_guarded(errbuf, errlen, [&] {
+    return qprofile_file_body(path, chunk_reads, max_reads, qual_offset, device, out, stats, errbuf, errlen);
+  });
+}
+int32_t dada2hip_qprofile_ncycle(const dada2hip_qprofile *p) { return p->ncycle; }
+const int64_t *dada2hip_qprofile_counts(const dada2hip_qprofile *p) { return p->counts.data(); }
+int64_t dada2hip_qprofile_reads_total(const dada2hip_qprofile *p) { return p->reads; }
+int64_t dada2hip_qprofile_profiled(const dada2hip_qprofile *p) { return p->profiled; }
+int32_t dada2hip_qprofile_qual_offset(const dada2hip_qprofile *p) { return p->qual_offset; }
+void dada2hip_qprofile_free(dada2hip_qprofile *p) { delete p; }
+
+int dada2hip_complexity_fastq(const char *path, int64_t chunk_reads, int64_t max_reads, int32_t kmer_size, int32_t window, int32_t by,
+                              int32_t device, double **out, int64_t *nout, int64_t *stats, char *errbuf, size_t errlen) {
+  return filter_files_guarded(errbuf, errlen, [&] {
+    return complexity_file_body(path, chunk_reads, max_reads, kmer_size, window, by, device, out, nout, stats, errbuf, errlen);
+  });
+}
+void dada2hip_complexity_free(double *values) { free(values); }
 
 }  // extern "C"

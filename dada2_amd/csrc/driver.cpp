@@ -3569,6 +3569,7 @@ int dada2hip_nwalign(const char *s1, const char *s2, int32_t match, int32_t mism
 extern "C++" {
 #include "stage_common.h"
 #include "read_pieces.h"
+#include "readqc_plain.h"
 }
 
 // ---- the sequence-table stage: collapseNoMismatch, nweval (R/multiSample.R:104-160, R/misc.R:216-225) ----
@@ -3585,6 +3586,9 @@ extern "C++" {
 
 // ---- removePrimers: primer search on both strands, orientation and the kept window (R/filter.R:81-233) ----
 #include "primers_host.h"
+
+// ---- read diagnostics: plotQualityProfile's per-cycle table, seqComplexity with a window (R/plot-methods.R:163-243, R/filter.R:1248-1275) ----
+#include "readqc_host.h"
 
 // ---- priors by sequence on a resident sample: names(uniques) %in% c(priors, pseudo_priors) (R/dada.R:335) ----
 #include "priors_host.h"

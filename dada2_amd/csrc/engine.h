@@ -674,6 +674,28 @@ struct PrimerOut { int32_t code, flip, first, last, hits[4]; };
 // starts (optional): [r * 8 + 2 k], [+ 1] the first and the last start of pattern k, 1-based on the strand it stands for
 void launch_primers(const PrimerArgs &A, int n, const uint8_t *d_seq, const long long *d_off, PrimerOut *d_out, int32_t *d_starts,
                     hipStream_t st);
+// read diagnostics (readqc.inc.hip).  A batch is n reads: the bytes of read r are qual (or seq)[off[r] .. off[r + 1]).
+// The quality table of a batch is tab[cycle * QP_NSCORE + letter - '!'], 64-bit counts that the kernel ADDS into (the host zeroes
+// it), `ncyc_pad` cycles of it: the batch's longest read rounded up to a whole tile.  bad[r] is set to 1 for a read with a letter
+// outside '!'..'~' (the host zeroes it too); such a letter is counted nowhere.
+constexpr int QP_NSCORE = 94;                 // the letters '!' .. '~'
+constexpr int QP_TILE = 64;                   // cycles per block: lane j of a wave reads cycle c0 + j of its read
+constexpr int QP_THREADS = 1024;              // sixteen waves share the block's LDS table through LDS atomics (fewer, larger blocks: the
+                                              // blocks' adds into the global table are what a launch waits for)
+constexpr int QP_ROW = QP_NSCORE + 1;         // the LDS row's stride, odd: the 32 lanes of a half wave that bump one score hit 32 different banks
+constexpr int QP_SLICE = 512;                 // reads per block of a launch's first dimension, until the grid has QP_GRID_X of them
+constexpr int QP_GRID_X = 1024;
+void launch_qprofile(int n, int ncyc_pad, const uint8_t *d_qual, const long long *d_off, unsigned long long *d_tab, int32_t *d_bad,
+                     hipStream_t st);
+// seqComplexity with a window: per read the smallest H = sum(-y log y) over the window starts 0, by, 2 by, ... <= len - window - 1
+// (0-based; `lo`), and H of the start len - window where that start is on the grid (`last`).  +infinity where no such window
+// exists, NaN where one of them holds no k-mer of A/C/G/T only.  ylogy[c], c = 0 .. window - k + 1: -y log y for y = c / (window - k
+// + 1), by the host's libm - the terms of a window whose k-mers all count; any other window's terms are the device's log.
+constexpr int CW_WINDOW_MAX = 1024;           // (the table of -y log y is the block's dynamic LDS: 8 KiB at most)
+constexpr int CW_GRID = 16384;                // blocks of one wave; a block takes reads blockIdx.x, + gridDim.x, ...
+struct ComplexityOut { double lo, last; };
+void launch_complexity_win(int n, int k, int window, int by, const uint8_t *d_seq, const long long *d_off, const double *d_ylogy,
+                           ComplexityOut *d_out, hipStream_t st);
 // priors by sequence (priors.inc.hip).  The prior sequences are packed like a sample's uniques; keys / groups as in SpeciesKeys (the
 // distinct prefix keys - the first min(32, length) bases -, ascending inside each key length's group; groups[g] = {key length, first
 // key, number of keys}).  The rows lie key by key: those of key k are rows key_row_off[k] .. key_row_off[k + 1], in the caller's

@@ -2909,6 +2909,7 @@ void launch_bimera_lr(const SampleDev &S, const int32_t *d_chunk_centre, const i
 #include "species.inc.hip"   // assignSpecies: the prefix-key seed over the resident references and the verification
 #include "filter.inc.hip"    // filterAndTrim: the per-read windows, counts and the word screen, the in-order EE sum, the k-mer histogram
 #include "primers.inc.hip"   // removePrimers: the bit planes of a read, the four-pattern search with a bit-sliced mismatch counter, the verdict
+#include "readqc.inc.hip"    // read diagnostics: the per-cycle quality table; the windowed k-mer complexity of a read
 #include "priors.inc.hip"    // priors by sequence: a lane per resident unique, its prefix key searched among the prior sequences' keys
 
 #include "rounds2.inc.hip"   // (the persistent round tail, rounds3.inc.hip, is the translation unit tail.hip)

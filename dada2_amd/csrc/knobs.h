@@ -76,6 +76,8 @@ struct Knobs {
   long long primers_piece = 0;        // DADA2HIP_PRIMERS_PIECE=n       removePrimers: reads per piece of a call (at least 1; at most, and unset, 65 536)
   long long primers_piece_bytes = 0;  // DADA2HIP_PRIMERS_PIECE_BYTES=n ... bases per piece (at least 1; at most, and unset, 32 MiB; a longer read is a piece of its own)
   long long primers_tile = 0;         // DADA2HIP_PRIMERS_TILE=n        ... chunks of 64 match starts per tile of a read (at least 1; at most, and unset, 64)
+  long long readqc_piece = 0;         // DADA2HIP_READQC_PIECE=n        read diagnostics: reads per piece of a call (at least 1; at most, and unset, 65 536)
+  long long readqc_piece_bytes = 0;   // DADA2HIP_READQC_PIECE_BYTES=n  ... bases per piece (at least 1; at most, and unset, 32 MiB; a longer read is a piece of its own)
   int species_cand = 1 << 20;         // DADA2HIP_SPECIES_CAND=n        assignSpecies: records of the candidate buffer and of the hit buffer (a launch that counts more is re-run in pieces)
   int species_chunk = 8192;           // DADA2HIP_SPECIES_CHUNK=n       ... distinct queries per pass over the references (at most 8 192: the presence bitmap is sized for it)
   int priors_lds_keys = 4096;         // DADA2HIP_PRIORS_LDS_KEYS=n     priors by sequence: up to n distinct prefix keys are searched in LDS, more in global memory (at most 6 144; 0 = always global; tests: the global path on a small set)
@@ -140,6 +142,7 @@ struct Knobs {
     k.tax_chunk = P("DADA2HIP_TAX_CHUNK"); k.filter_piece = P("DADA2HIP_FILTER_PIECE"); k.filter_piece_bytes = P("DADA2HIP_FILTER_PIECE_BYTES");
     k.nw_ring = P("DADA2HIP_NW_RING");
     k.primers_piece = P("DADA2HIP_PRIMERS_PIECE"); k.primers_piece_bytes = P("DADA2HIP_PRIMERS_PIECE_BYTES"); k.primers_tile = P("DADA2HIP_PRIMERS_TILE");
+    k.readqc_piece = P("DADA2HIP_READQC_PIECE"); k.readqc_piece_bytes = P("DADA2HIP_READQC_PIECE_BYTES");
     k.species_cand = I("DADA2HIP_SPECIES_CAND", 1 << 20); k.species_chunk = I("DADA2HIP_SPECIES_CHUNK", 8192);
     k.priors_lds_keys = I("DADA2HIP_PRIORS_LDS_KEYS", 4096); k.priors_grid = I("DADA2HIP_PRIORS_GRID", 0);
     if (const char *e = S("DADA2HIP_DEREP_INFLATE")) k.derep_zlib = !std::strcmp(e, "zlib");

@@ -1,4 +1,4 @@
-// stage_stats.h — the words of the five stages' `stats` arrays (include/dada2hip.h says what each holds), named once.  Plain C++:
+// stage_stats.h — the words of the stages' `stats` arrays (include/dada2hip.h says what each holds), named once.  Plain C++:
 // driver.cpp takes it through stage_common.h, derep.cpp - whose file-level entries add the calls' words up over the chunks of a
 // file - directly.  A word's position is ABI: a new word goes in front of its enum's *_COUNT, never between two others.
 #pragma once
@@ -18,6 +18,11 @@ enum { PS_IN = 0, PS_KEPT, PS_CODE1, PS_FLIPPED = 6, PS_MULTI, PS_HITS_FWD, PS_H
        PS_US_DOWN, PS_US_PARSE, PS_US_DEFLATE, PS_US_WRITE, PS_US_TOTAL, PS_US_INFLATE, PS_COUNT };
 enum { QS_GIVEN = 0, QS_KEPT, QS_KEYS, QS_LDS, QS_SET, QS_BLOCKS, QS_US_PACK, QS_US_DEVICE, QS_US_KERNEL, QS_US_TOTAL, QS_COUNT };   // dada2hip_sample_set_prior_seqs
 static_assert(QS_COUNT <= DADA2HIP_PRIOR_SEQS_NSTATS, "stats words");
+// the read diagnostics (dada2hip_qprofile_*, dada2hip_complexity_*): RQ_US_PARSE and behind are the file level's
+enum { RQ_IN = 0, RQ_PROFILED, RQ_PIECES, RQ_CYCLES, RQ_BYTES, RQ_US_UP, RQ_US_KERNEL, RQ_US_DOWN, RQ_US_PARSE, RQ_US_TOTAL, RQ_US_INFLATE,
+       RQ_COUNT };
+static_assert(RQ_COUNT <= DADA2HIP_READQC_NSTATS && RQ_IN == FS_IN && RQ_PROFILED == FS_KEPT, "stats words; reads in and profiled where a file's reads in and kept are");
+enum { RQ_CALL_FIRST = RQ_PIECES, RQ_CALL_LAST = RQ_US_DOWN };   // the words of a chunk's call that a file adds up (RQ_CYCLES: the largest)
 // How a file adds its chunks' calls up.  Filter: the words of the context are taken, the call's total is the file's own, every other
 // word adds; of a pair's second file only the bytes and the call's clocks add.  Primers: every word of the call adds.
 enum { FS_TAKEN_FIRST = FS_KEYS, FS_TAKEN_LAST = FS_LDS, FS_CLOCK_FIRST = FS_BYTES, FS_CLOCK_LAST = FS_US_DOWN, PS_CALL_LAST = PS_US_DOWN };

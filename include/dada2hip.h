@@ -27,6 +27,8 @@
  *   dada2hip_filter_*       <- filterAndTrim() / fastqFilter() / fastqPairedFilter() / isPhiX() / seqComplexity()  R/filter.R:402-1275 on
  *                              C_matchRef / C_matrixEE (src/filter.cpp:7-49)
  *   dada2hip_primers_*      <- removePrimers()  R/filter.R:81-233 (vmatchPattern without indels, restated)
+ *   dada2hip_qprofile_*     <- the data of plotQualityProfile()  R/plot-methods.R:163-243 (ShortRead qa()'s perCycle$quality, restated)
+ *   dada2hip_complexity_*   <- seqComplexity() with window / by, plotComplexity()'s data  R/filter.R:1248-1275, R/plot-methods.R:293-299
  *
  * Conventions: plain C, no exceptions cross the boundary.  Every call returns 0 on success or a
  * non-zero code with a NUL-terminated message in `errbuf` (the reference's Rcpp::stop texts are
@@ -66,6 +68,8 @@
  *   DADA2HIP_PRIMERS_PIECE=<n>         dada2hip_primers_reads: reads per piece of a call (at least 1; default and at most 65 536)
  *   DADA2HIP_PRIMERS_PIECE_BYTES=<n>   ... bases per piece (at least 1; default and at most 32 MiB; a longer read is a piece of its own)
  *   DADA2HIP_PRIMERS_TILE=<n>          ... chunks of 64 match starts per tile of a read (at least 1; default and at most 64)
+ *   DADA2HIP_READQC_PIECE=<n>          dada2hip_qprofile_reads, dada2hip_complexity_reads: reads per piece of a call (at least 1; default and at most 65 536)
+ *   DADA2HIP_READQC_PIECE_BYTES=<n>    ... bases per piece (at least 1; default and at most 32 MiB; a longer read is a piece of its own)
  *   DADA2HIP_PRIORS_LDS_KEYS=<n>       dada2hip_sample_set_prior_seqs: up to n distinct prefix keys are searched in LDS, more in global
  *                                      memory (default 4 096, at most 6 144; 0 = always global memory)
  *   DADA2HIP_PROFILE=1, DADA2HIP_V2_SUMMARY, DADA2HIP_V2_DEBUG   per-launch device times in the stats; traces on stderr
@@ -630,6 +634,51 @@ int dada2hip_primers_reads(int64_t n, const char *seq, const int64_t *offsets, c
 int dada2hip_primers_fastq(const char *in, const char *out, const dada2hip_primer_params *params, int32_t compress,
                            int64_t chunk_reads, int32_t device, int64_t *reads_in, int64_t *reads_out, int64_t *stats,
                            char *errbuf, size_t errlen);
+
+/* ---- read diagnostics: the data of plotQualityProfile and plotComplexity (R/plot-methods.R:163-243, :293-299; R/filter.R:1248-1275) ----
+ * Nothing is drawn here; dada2_amd/readqc.py restates the statistics of the R code on these numbers.
+ * dada2hip_qprofile_reads: n reads' quality strings, read r being qual[offsets[r] .. offsets[r + 1]).  counts[c * 94 + letter - 33],
+ * c < ncycle, is SET to the number of reads whose quality letter at cycle c + 1 is `letter` ('!' .. '~'; ShortRead qa()'s
+ * perCycle$quality before an offset is taken off); cycles from the longest read on stay 0.  A letter outside '!'..'~' is
+ * DADA2HIP_ERR_INPUT and the message names the read; a read longer than ncycle, or than 262 144, is refused.
+ * dada2hip_qprofile_fastq: the table of a FASTQ file (plain or gzip), read in chunks of chunk_reads records (<= 0: 100 000) with
+ * the reader of dada2hip_filter_fastq, the next chunk parsed under this chunk's kernel.  The first max_reads records are profiled
+ * (0: all of them; the reference profiles a random sample of that size), the whole file is counted.  qual_offset 33, 64 or 0 =
+ * Auto (dada2hip_derep_fastq's rule, on the first chunk).  Accessors: _ncycle the longest profiled read, _counts the table
+ * [ncycle x 94] as above, _reads the records of the file (the reference's rc), _profiled those counted in the table,
+ * _qual_offset the offset settled.
+ * dada2hip_complexity_reads: seqComplexity(seqs, kmerSize, window, by) of n sequences, sequence r being seq[offsets[r] ..
+ * offsets[r + 1]).  window 0 is window = NULL: dada2hip_filter_reads' complexity of the whole sequence.  Otherwise the R loop with
+ * its quirks: the value starts at 4^k; window starts i = 1, 1 + by, ... <= max(width) - window, the maximum over the sequences of
+ * THE CALL; a sequence is tested at i only if it is at least i + window - 1 long - so one shorter than the window keeps 4^k, and
+ * one of the maximal length never has its last window tested; k-mers with a letter other than upper-case A/C/G/T are not counted,
+ * and a tested window without a countable k-mer makes the value NaN for good.  kmer_size 0 means 2.  DADA2HIP_ERR_INPUT:
+ * kmer_size >= window ("The window over which kmer frequency is calculated must be larger than the kmerSize."), max(width) -
+ * window < 1 (R's seq() stops), by < 1.  DADA2HIP_ERR_UNSUPPORTED: kmer_size outside 0..4, window above 1 024.
+ * dada2hip_complexity_fastq: the same of the first max_reads records of a file (0: all), the maximum taken over those records;
+ * *out is an array of *nout doubles for dada2hip_complexity_free.
+ * stats (optional, DADA2HIP_READQC_NSTATS int64 words): [0] reads in (of a file: its records), [1] reads profiled, [2] pieces,
+ * [3] cycles of the table (complexity: the longest sequence), [4] bytes copied to the device, [5] host microseconds of the upload,
+ * [6] device microseconds of the kernel, [7] host microseconds of the download, [8] of parsing, [9] of the whole call, [10] of
+ * opening the input. */
+#define DADA2HIP_READQC_NSTATS 16
+#define DADA2HIP_QPROFILE_NSCORE 94
+typedef struct dada2hip_qprofile dada2hip_qprofile;
+int dada2hip_qprofile_reads(int64_t n, const char *qual, const int64_t *offsets, int32_t device, int32_t ncycle, int64_t *counts,
+                            int64_t *stats, char *errbuf, size_t errlen);
+int dada2hip_qprofile_fastq(const char *path, int64_t chunk_reads, int64_t max_reads, int32_t qual_offset, int32_t device,
+                            dada2hip_qprofile **out, int64_t *stats, char *errbuf, size_t errlen);
+int32_t dada2hip_qprofile_ncycle(const dada2hip_qprofile *p);
+const int64_t *dada2hip_qprofile_counts(const dada2hip_qprofile *p);
+int64_t dada2hip_qprofile_reads_total(const dada2hip_qprofile *p);
+int64_t dada2hip_qprofile_profiled(const dada2hip_qprofile *p);
+int32_t dada2hip_qprofile_qual_offset(const dada2hip_qprofile *p);
+void dada2hip_qprofile_free(dada2hip_qprofile *p);
+int dada2hip_complexity_reads(int64_t n, const char *seq, const int64_t *offsets, int32_t kmer_size, int32_t window, int32_t by,
+                              int32_t device, double *complexity, int64_t *stats, char *errbuf, size_t errlen);
+int dada2hip_complexity_fastq(const char *path, int64_t chunk_reads, int64_t max_reads, int32_t kmer_size, int32_t window, int32_t by,
+                              int32_t device, double **out, int64_t *nout, int64_t *stats, char *errbuf, size_t errlen);
+void dada2hip_complexity_free(double *values);
 
 /* One b_compare round exposed for kernel-level parity tests and for bench.py's roofline leg:
  * compares every unique of `s` against unique `centre` exactly as CompareParallel does
