@@ -129,7 +129,13 @@ EXPORTS = [
     "dada2hip_qprofile_reads", "dada2hip_qprofile_fastq", "dada2hip_qprofile_ncycle", "dada2hip_qprofile_counts",
     "dada2hip_qprofile_reads_total", "dada2hip_qprofile_profiled", "dada2hip_qprofile_qual_offset", "dada2hip_qprofile_free",
     "dada2hip_complexity_reads", "dada2hip_complexity_fastq", "dada2hip_complexity_free",
+    "dada2hip_bimera_denovo", "dada2hip_bimera_worklist_probe", "dada2hip_bimera_fold_probe",
 ]
+
+BIMERA_DENOVO_NSTATS = 16   # DADA2HIP_BIMERA_DENOVO_NSTATS
+# the int64 words of dada2hip_bimera_denovo's stats, in order; aligner_route: 1 = k_nw_ad in its bimera mode, 2 = lane kernel + k_bimera_lr
+BIMERA_DENOVO_STATS = ("sequences", "rows", "queries", "pairs_possible", "pairs_aligned", "windows", "launches", "flagged", "aligner_route",
+                       "per", "slot_budget", "pack_us", "device_us", "kernel_device_us", "total_us")
 
 PRIOR_SEQS_NSTATS = 16   # DADA2HIP_PRIOR_SEQS_NSTATS
 # the int64 words of dada2hip_sample_prior_seqs_stats, in order
@@ -363,6 +369,9 @@ def lib():
     L.dada2hip_primers_fastq.argtypes = [cp, cp, C.POINTER(CPrimerParams), ip, C.c_int64, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                          vp, cp, C.c_size_t]
     L.dada2hip_derep_combine.argtypes = [ip, C.POINTER(CDerepView), C.POINTER(vp), vp, cp, C.c_size_t]
+    L.dada2hip_bimera_denovo.argtypes = [ip, ip, vp, C.POINTER(cp), C.c_double, C.c_double, ip, ip, ip, ip, ip, ip, ip, ip, vp, vp, cp, C.c_size_t]
+    L.dada2hip_bimera_worklist_probe.argtypes = [ip, vp, vp, vp, ip, vp, ip, ip, ip, ip, vp, vp, cp, C.c_size_t]
+    L.dada2hip_bimera_fold_probe.argtypes = [ip, vp, vp, ip, vp, ip, ip, vp, vp, ip, ip, ip, ip, vp, vp, vp, vp, vp, cp, C.c_size_t]
     L.dada2hip_sample_set_prior_seqs.argtypes = [vp, ip, vp, vp, vp, C.POINTER(ip), cp, C.c_size_t]
     L.dada2hip_sample_prior_seqs_stats.argtypes = [vp, vp]
     L.dada2hip_sample_prior_seqs_stats.restype = None

@@ -534,6 +534,185 @@ def is_bimera_denovo_table(mat, seqs, min_sample_fraction=0.9, ignore_n_negative
     return (nflag >= nsam) | ((nflag > 0) & (nflag >= (nsam - ignore_n_negatives) * min_sample_fraction))
 
 
+def _is_table(obj):
+    """A (mat, seqs) sequence table: a two-dimensional array with its column names."""
+    return (isinstance(obj, tuple) and len(obj) == 2 and getattr(obj[0], "ndim", 0) == 2 and not isinstance(obj[1], np.ndarray)
+            and len(obj[1]) == obj[0].shape[1] and all(isinstance(s, str) for s in obj[1]))
+
+
+def _input_uniques(obj, seqs=None):
+    """(sequences, abundances) of ``obj`` as given - duplicates kept, input order: what getSequences sees."""
+    if seqs is not None:
+        obj = (np.asarray(obj), list(seqs))
+    if isinstance(obj, DadaResult):
+        s, a = obj.clustering["sequence"], obj.clustering["abundance"]
+    elif isinstance(obj, Derep):
+        s, a = obj.seqs, obj.abundances
+    elif isinstance(obj, dict):
+        s, a = list(obj.keys()), list(obj.values())
+    elif _is_table(obj):
+        s, a = obj[1], np.asarray(obj[0]).sum(axis=0, dtype=np.int64)   # as.integer(colSums(object))
+    elif isinstance(obj, (tuple, list)) and len(obj) == 2 and not isinstance(obj[0], str) and len(obj[0]) == len(obj[1]):
+        s, a = obj
+    else:
+        raise ValueError("Unrecognized format: Requires a {sequence: abundance} mapping, a (sequences, abundances) pair, a DadaResult, "
+                         "a Derep or a (mat, seqs) sequence table.")
+    s = [str(x) for x in s]
+    a = np.asarray(a, dtype=np.int64).reshape(-1)
+    if len(s) != a.size:
+        raise ValueError("One abundance per sequence is required.")
+    if a.size and (a.max() > np.iinfo(np.int32).max or a.min() < 0):
+        raise _lib.Dada2HipError(1, "dada2hip: an abundance is negative or exceeds the integer range.")
+    return s, a
+
+
+def get_uniques(obj, seqs=None):
+    """getUniques (R/misc.R:33-62): (sequences, int32 abundances) of a {sequence: abundance} mapping, a (sequences, abundances)
+    pair, a DadaResult (its clustering's sequence / abundance), a Derep or a sequence table - ``(mat, seqs)``, or ``mat`` with
+    ``seqs=`` - whose abundances are the column sums.  A sequence given more than once is merged and its abundances summed, the
+    result then standing in ascending byte order of the sequences, as ``tapply(unqs, names(unqs), sum)`` leaves it (:55)."""
+    s, a = _input_uniques(obj, seqs)
+    if len(set(s)) == len(s):
+        return s, a.astype(np.int32)
+    summed = {}
+    for x, v in zip(s, a):
+        summed[x] = summed.get(x, 0) + int(v)
+    keys = sorted(summed, key=lambda x: x.encode("ascii"))
+    tot = np.array([summed[k] for k in keys], dtype=np.int64)
+    if tot.max() > np.iinfo(np.int32).max:
+        raise _lib.Dada2HipError(1, "dada2hip: an abundance is negative or exceeds the integer range.")
+    return keys, tot.astype(np.int32)
+
+
+def bimera_denovo_rows(mat, seqs, min_fold_parent_over_abundance=2, min_parent_abundance=8, allow_one_off=False,
+                       min_one_off_parent_distance=4, max_shift=16, match=5, mismatch=-4, gap_p=-8, skip_zero=False, device: int = 0,
+                       stats: dict = None):
+    """dada2hip_bimera_denovo: isBimeraDenovo (R/chimeras.R:105-154) on every row of the [rows, sequences] table ``mat`` with the
+    sequences resident once - bool [rows, sequences].  The sequences must be distinct.  ``skip_zero``: zero cells are FALSE without
+    work.  ``stats`` (a dict) receives the library's counters (_lib.BIMERA_DENOVO_STATS)."""
+    m = np.asfortranarray(np.asarray(mat, dtype=np.int32))
+    if m.ndim != 2 or m.shape[1] != len(seqs):
+        raise ValueError("The sequence table must have one column per sequence.")
+    nrow, ncol = m.shape
+    flags = np.zeros((nrow, ncol), dtype=np.uint8, order="F")
+    st = np.zeros(_lib.BIMERA_DENOVO_NSTATS, dtype=np.int64)
+    eb = C.create_string_buffer(_EB)
+    _lib.check(_lib.lib().dada2hip_bimera_denovo(nrow, ncol, m.ctypes.data, _charpp(list(seqs)), float(min_fold_parent_over_abundance),
+                                                 float(min_parent_abundance), int(bool(allow_one_off)), int(min_one_off_parent_distance),
+                                                 int(match), int(mismatch), int(gap_p), int(max_shift), int(bool(skip_zero)), device,
+                                                 flags.ctypes.data, st.ctypes.data, eb, _EB), eb)
+    if stats is not None:
+        stats.update({k: int(v) for k, v in zip(_lib.BIMERA_DENOVO_STATS, st)})
+    return flags.astype(bool)
+
+
+def is_bimera_denovo(unqs, min_fold_parent_over_abundance=2, min_parent_abundance=8, allow_one_off=False,
+                     min_one_off_parent_distance=4, max_shift=16, match=5, mismatch=-4, gap_p=-8, device: int = 0, stats: dict = None,
+                     seqs=None):
+    """isBimeraDenovo (R/chimeras.R:105-154): a bool array with one entry per INPUT sequence of ``unqs`` (any form get_uniques
+    takes), TRUE where the sequence is a two-parent bimera of sequences more than ``min_fold_parent_over_abundance`` times as
+    abundant and more abundant than ``min_parent_abundance``.  A sequence given more than once gets the answer of its merged entry
+    (``seqs.input %in% seqs[bims]``, :150)."""
+    s_in, _ = _input_uniques(unqs, seqs)
+    s, a = get_uniques(unqs, seqs)
+    if not s:
+        return np.zeros(0, dtype=bool)
+    bim = bimera_denovo_rows(a.reshape(1, -1), s, min_fold_parent_over_abundance, min_parent_abundance, allow_one_off,
+                             min_one_off_parent_distance, max_shift, match, mismatch, gap_p, False, device, stats)[0]
+    if s_in == s:
+        return bim
+    flagged = {x for x, b in zip(s, bim) if b}
+    return np.array([x in flagged for x in s_in], dtype=bool)
+
+
+def remove_bimera_denovo(unqs, method="consensus", seqs=None, **kw):
+    """removeBimeraDenovo (R/chimeras.R:294-346).  A sequence table - ``(mat, seqs)``, or ``mat`` with ``seqs=`` - comes back as
+    (mat, seqs): with "pooled" (is_bimera_denovo on the column sums) and "consensus" (is_bimera_denovo_table, whose own defaults
+    are 1.5 and 2) without the flagged columns; with "per-sample" every row is run on its own, the flagged cells are zeroed and the
+    columns left without a count are dropped (:329-332).  Every other input goes through is_bimera_denovo whatever ``method`` says
+    and comes back as (sequences, int32 abundances) in input order without the flagged entries.  ``kw`` goes to the function that
+    decides."""
+    table = seqs is not None or _is_table(unqs)
+    if not table:
+        s, a = _input_uniques(unqs)
+        keep = ~is_bimera_denovo((s, a), **kw)
+        return [x for x, k in zip(s, keep) if k], a[keep].astype(np.int32)
+    mat, names = (np.asarray(unqs), list(seqs)) if seqs is not None else (np.asarray(unqs[0]), list(unqs[1]))
+    if mat.ndim != 2 or mat.shape[1] != len(names):
+        raise ValueError("The sequence table must have one column per sequence.")
+    if method == "pooled":
+        keep = ~is_bimera_denovo((mat, names), **kw)
+    elif method == "consensus":
+        keep = ~np.asarray(is_bimera_denovo_table(mat, names, **kw), dtype=bool)
+    elif method == "per-sample":
+        if len(set(names)) != len(names):
+            raise ValueError("Duplicate sequences detected in input.")
+        bim = bimera_denovo_rows(mat, names, skip_zero=True, **kw)
+        out = np.array(mat, copy=True)
+        out[bim] = 0
+        keep = out.sum(axis=0, dtype=np.int64) != 0
+        return np.ascontiguousarray(out[:, keep]), [x for x, k in zip(names, keep) if k]
+    else:
+        raise ValueError("Valid values for method: 'pooled', 'consensus', or 'per-sample'")
+    return np.ascontiguousarray(mat[:, keep]), [x for x, k in zip(names, keep) if k]
+
+
+def is_shift_denovo(unqs, min_overlap=20, flag_subseqs=False, device: int = 0, seqs=None):
+    """isShiftDenovo (R/chimeras.R:380-399): a bool array with one entry per input sequence, TRUE where the sequence equals a more
+    abundant one up to an overall shift - isShiftedPair (:412-417): the unbanded ends-free alignment with the default scores has no
+    mismatch and no indel, at least ``min_overlap`` matches, and fewer matches than either sequence is long.  ``flag_subseqs`` is
+    accepted and has NO effect, as in the reference: isShiftDenovo never passes it on to isShift (:391), so a strict subsequence is
+    FALSE either way.  A pair whose best gapless diagonal cannot be an exact optimal alignment (dada2hip_collapse_pairs: m_max <
+    min_overlap or G > match * m_max) is FALSE without an alignment; the others go through dada2hip_nweval."""
+    del flag_subseqs
+    s_in, _ = _input_uniques(unqs, seqs)
+    s, a = get_uniques(unqs, seqs)
+    n = len(s)
+    order = np.argsort(-a.astype(np.int64), kind="stable")
+    ra = a[order]
+    npar = np.searchsorted(-ra.astype(np.int64), -a.astype(np.int64), side="left")    # parents of j: abunds > abund_j, ranks [0, npar[j])
+    shift = np.zeros(n, dtype=bool)
+    CH = 1 << 20
+    qi, pi = [], []
+
+    def flush():
+        if not qi:
+            return
+        q = np.concatenate(qi)
+        p = np.concatenate(pi)
+        qi.clear()
+        pi.clear()
+        qs, ps = [s[int(k)] for k in q], [s[int(k)] for k in p]
+        cp = collapse_pairs(qs, ps, min_overlap=max(int(min_overlap), 1), device=device)
+        cand = np.flatnonzero((cp[:, 2] >= min_overlap) & (cp[:, 1] <= 5 * cp[:, 2]))
+        if cand.size:
+            cq, cpar = [qs[int(k)] for k in cand], [ps[int(k)] for k in cand]
+            ev = nweval(cq, cpar, band=-1, device=device).reshape(-1, 3)
+            l1 = np.array([len(x) for x in cq])
+            l2 = np.array([len(x) for x in cpar])
+            ok = (ev[:, 0] < l1) & (ev[:, 0] < l2) & (ev[:, 0] >= min_overlap) & (ev[:, 1] == 0) & (ev[:, 2] == 0)
+            shift[q[cand[ok]]] = True
+
+    pending = 0
+    for j in range(n):
+        k = int(npar[j])
+        at = 0
+        while at < k:
+            take = min(k - at, CH - pending)
+            qi.append(np.full(take, j, dtype=np.int64))
+            pi.append(order[at:at + take].astype(np.int64))
+            at += take
+            pending += take
+            if pending == CH:
+                flush()
+                pending = 0
+    flush()
+    if s_in == s:
+        return shift
+    flagged = {x for x, b in zip(s, shift) if b}
+    return np.array([x in flagged for x in s_in], dtype=bool)
+
+
 def merge_pairs(dadaF: DadaResult, derepF: Derep, dadaR: DadaResult, derepR: Derep, min_overlap=12, max_mismatch=0,
                 return_rejects=False, just_concatenate=False, trim_overhang=False, device: int = 0):
     """mergePairs() for one sample (R/paired.R:92-201) through dada2hip_merge_pairs: a list of dict rows (sequence,

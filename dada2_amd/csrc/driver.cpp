@@ -3570,6 +3570,7 @@ extern "C++" {
 #include "stage_common.h"
 #include "read_pieces.h"
 #include "readqc_plain.h"
+#include "bimera_plain.h"
 }
 
 // ---- the sequence-table stage: collapseNoMismatch, nweval (R/multiSample.R:104-160, R/misc.R:216-225) ----
@@ -3592,6 +3593,9 @@ extern "C++" {
 
 // ---- priors by sequence on a resident sample: names(uniques) %in% c(priors, pseudo_priors) (R/dada.R:335) ----
 #include "priors_host.h"
+
+// ---- isBimeraDenovo on a uniques vector or on every row of a table: parents as a prefix of the ranking (R/chimeras.R:105-154, :321-333) ----
+#include "bimera_denovo_host.h"
 
 // ---- result getters ------------------------------------------------------------------------------
 int32_t dada2hip_result_nclust(const dada2hip_result *r) { return r->nclust; }

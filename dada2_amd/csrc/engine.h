@@ -710,6 +710,24 @@ struct PriorKeys {
 constexpr int PRIOR_LDS_KEYS_MAX = 6144;      // 48 KiB of keys per block
 int launch_prior_match(const SampleDev &S, const PriorKeys &K, bool lds, int grid_cap, const uint8_t *d_or_flags, int32_t *d_first_match,
                        hipStream_t st);
+// isBimeraDenovo on a resident lite sample (bimera_denovo.inc.hip): the work lists of one launch - nq live queries x wr parent ranks
+// from r0, `per` slots to a chunk of the aligner - and the fold of the aligner's five-word records into the queries' running maxima
+struct BimeraFold {
+  const int32_t *live;       // the launch's queries
+  int nq, r0, wr;            // ... their number; the launch's ranks [r0, r0 + wr)
+  const int32_t *work;       // nq * wr slots and their records
+  const int32_t *rec;
+  const int32_t *len, *P;
+  int allow_one_off, min_one_off_par_dist;
+  int32_t *maxima;           // six words per sequence: max_left, max_right, oo_max_left, oo_max_right, oo_max_left_oo, oo_max_right_oo
+  uint8_t *flags;
+  unsigned long long *aligned;   // slots that named a parent, counted up
+  int last;                  // this launch ends the window for its queries: compact them
+  int32_t *next_live, *n_next;
+};
+void launch_bimera_worklist(const int32_t *d_live, int nq, int r0, int wr, int per, const int32_t *d_rank, const int32_t *d_P,
+                            const uint8_t *d_flags, int32_t *d_chunk_centre, int32_t *d_work, hipStream_t st);
+void launch_bimera_fold(const BimeraFold &F, hipStream_t st);
 void launch_calc_pA(int n, const int32_t *d_reads, const double *d_E, const uint8_t *d_prior, double *d_out,
                     hipStream_t st);
 

@@ -18,6 +18,10 @@ enum { PS_IN = 0, PS_KEPT, PS_CODE1, PS_FLIPPED = 6, PS_MULTI, PS_HITS_FWD, PS_H
        PS_US_DOWN, PS_US_PARSE, PS_US_DEFLATE, PS_US_WRITE, PS_US_TOTAL, PS_US_INFLATE, PS_COUNT };
 enum { QS_GIVEN = 0, QS_KEPT, QS_KEYS, QS_LDS, QS_SET, QS_BLOCKS, QS_US_PACK, QS_US_DEVICE, QS_US_KERNEL, QS_US_TOTAL, QS_COUNT };   // dada2hip_sample_set_prior_seqs
 static_assert(QS_COUNT <= DADA2HIP_PRIOR_SEQS_NSTATS, "stats words");
+// dada2hip_bimera_denovo: BD_ROUTE 1 = k_nw_ad in its bimera mode, 2 = the lane kernel + k_bimera_lr; BD_PER: slots to a chunk of the aligner
+enum { BD_SEQS = 0, BD_ROWS, BD_QUERIES, BD_PAIRS_POSSIBLE, BD_PAIRS_ALIGNED, BD_WINDOWS, BD_LAUNCHES, BD_FLAGGED, BD_ROUTE, BD_PER, BD_SLOTS,
+       BD_US_PACK, BD_US_DEVICE, BD_US_KERNEL, BD_US_TOTAL, BD_COUNT };
+static_assert(BD_COUNT <= DADA2HIP_BIMERA_DENOVO_NSTATS, "stats words");
 // the read diagnostics (dada2hip_qprofile_*, dada2hip_complexity_*): RQ_US_PARSE and behind are the file level's
 enum { RQ_IN = 0, RQ_PROFILED, RQ_PIECES, RQ_CYCLES, RQ_BYTES, RQ_US_UP, RQ_US_KERNEL, RQ_US_DOWN, RQ_US_PARSE, RQ_US_TOTAL, RQ_US_INFLATE,
        RQ_COUNT };

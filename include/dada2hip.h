@@ -72,6 +72,8 @@
  *   DADA2HIP_READQC_PIECE_BYTES=<n>    ... bases per piece (at least 1; default and at most 32 MiB; a longer read is a piece of its own)
  *   DADA2HIP_PRIORS_LDS_KEYS=<n>       dada2hip_sample_set_prior_seqs: up to n distinct prefix keys are searched in LDS, more in global
  *                                      memory (default 4 096, at most 6 144; 0 = always global memory)
+ *   DADA2HIP_BIMERA_SLOTS=<n>          dada2hip_bimera_denovo: work slots per launch (at least one chunk of the aligner; default and at most
+ *                                      what a launch of dada2hip_table_bimera2 holds)
  *   DADA2HIP_PROFILE=1, DADA2HIP_V2_SUMMARY, DADA2HIP_V2_DEBUG   per-launch device times in the stats; traces on stderr
  * Test / tuning knobs (sizes of rings and grids, forced growth paths, injected failures) are listed with their meaning in
  * knobs.h and DESIGN.md §10b; they are not part of the interface.
@@ -344,6 +346,41 @@ int dada2hip_is_bimera(const char *sq, int32_t npars, const char *const *pars, i
 int dada2hip_bimera_pairs(int32_t n, const char *const *queries, const char *const *parents, int32_t allow_one_off,
                           int32_t match, int32_t mismatch, int32_t gap_p, int32_t max_shift, int32_t device, int32_t *out,
                           char *errbuf, size_t errlen);
+
+/* dada2hip_bimera_denovo == isBimeraDenovo (R/chimeras.R:105-154) on every row of an integer table, the sequences resident once:
+ * mat is nrow x ncol, column-major as for dada2hip_table_bimera2 (nrow = 1: a uniques vector); flags[i + j * nrow] = 1 when
+ * sequence j is a bimera of row i's more abundant sequences.  The parents of query j in a row are the sequences k with
+ * mat[k] > min_fold * mat[j] and mat[k] > min_parent_abund (:127: both compared as doubles, both strict); fewer than two parents
+ * give 0 without an alignment (:128).  That set is a prefix of the row's ranking by abundance, so the device is told the ranking
+ * and one integer per query, visits the parents in windows of ranks - most abundant first - and drops a query from the work as
+ * soon as a model is complete (C_is_bimera's running maxima, src/chimera.cpp:29-50, only grow: the answer is the reference's).
+ * skip_zero: queries of abundance 0 get 0 without work (removeBimeraDenovo's "per-sample" zeroes those cells anyway).
+ * Abundances must not be negative; the sequences are A/C/G/T only and max_shift is not 0, as for dada2hip_table_bimera2.
+ * stats (optional, DADA2HIP_BIMERA_DENOVO_NSTATS int64): [0] sequences, [1] rows, [2] queries with at least two parents,
+ * [3] pairs possible (the sum of their parents), [4] pairs aligned, [5] windows, [6] launches of the aligner, [7] flags set,
+ * [8] the aligner's route (1 = k_nw_ad in its bimera mode, 2 = the lane kernel + k_bimera_lr), [9] slots per chunk of the aligner,
+ * [10] the slot budget of a launch, [11] us of ranking and packing, [12] us of device work as the host sees it, [13] us of kernels
+ * (event-timed under DADA2HIP_PROFILE=1, else 0), [14] us in total. */
+#define DADA2HIP_BIMERA_DENOVO_NSTATS 16
+int dada2hip_bimera_denovo(int32_t nrow, int32_t ncol, const int32_t *mat, const char *const *seqs, double min_fold,
+                           double min_parent_abund, int32_t allow_one_off, int32_t min_one_off_par_dist, int32_t match,
+                           int32_t mismatch, int32_t gap_p, int32_t max_shift, int32_t skip_zero, int32_t device, uint8_t *flags,
+                           int64_t *stats, char *errbuf, size_t errlen);
+
+/* The two kernels of dada2hip_bimera_denovo on arrays the caller makes up, so that they can be held to restatements on hand-made
+ * records (tests/).  n sequences; nq live queries `live`, parent ranks [r0, r0 + wr), wr a multiple of per, nq * wr <= 2^23.
+ * worklist_probe: rank[n], P[n], flags[n] in; chunk_centre[nq * wr / per] and work[nq * wr] out (slot (q, r): rank[r] while
+ * r < P[q] and flags[q] == 0, else -1).  fold_probe: work[nq * wr], rec[5 * nq * wr] (left, right, left_oo, right_oo, hamming of
+ * each slot that names a parent), len[n], P[n] in; maxima[6 n] and flags[n] in and out; with last != 0 the queries still unflagged
+ * with P > r0 + wr go to next_live (any order; the rest of its nq entries is -1) and are counted in *n_next; *aligned = the slots
+ * that named a parent. */
+int dada2hip_bimera_worklist_probe(int32_t n, const int32_t *rank, const int32_t *P, const uint8_t *flags, int32_t nq,
+                                   const int32_t *live, int32_t r0, int32_t wr, int32_t per, int32_t device, int32_t *chunk_centre,
+                                   int32_t *work, char *errbuf, size_t errlen);
+int dada2hip_bimera_fold_probe(int32_t n, const int32_t *len, const int32_t *P, int32_t nq, const int32_t *live, int32_t r0,
+                               int32_t wr, const int32_t *work, const int32_t *rec, int32_t allow_one_off,
+                               int32_t min_one_off_par_dist, int32_t last, int32_t device, int32_t *maxima, uint8_t *flags,
+                               int32_t *next_live, int32_t *n_next, int64_t *aligned, char *errbuf, size_t errlen);
 
 /* ---- dereplication front-end: the step before dada() ----------------------------------------
  * dada2hip_derep_fastq == derepFastq(fl, n = chunk_reads, qualityType = "Auto" | offset) (R/sequenceIO.R:45-124 on top of
