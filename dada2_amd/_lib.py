@@ -124,6 +124,7 @@ EXPORTS = [
     "dada2hip_species_open", "dada2hip_species_free", "dada2hip_species_match", "dada2hip_species_hits_offsets",
     "dada2hip_species_hits_refs", "dada2hip_species_hits_free",
     "dada2hip_filter_open", "dada2hip_filter_free", "dada2hip_filter_reads", "dada2hip_filter_fastq", "dada2hip_filter_fastq_paired",
+    "dada2hip_filter_reads_oriented", "dada2hip_filter_fastq_oriented", "dada2hip_filter_fastq_paired_ex",
     "dada2hip_primers_reads", "dada2hip_primers_fastq",
     "dada2hip_derep_combine", "dada2hip_sample_set_prior_seqs", "dada2hip_sample_prior_seqs_stats",
     "dada2hip_qprofile_reads", "dada2hip_qprofile_fastq", "dada2hip_qprofile_ncycle", "dada2hip_qprofile_counts",
@@ -365,6 +366,12 @@ def lib():
                                         vp, cp, C.c_size_t]
     L.dada2hip_filter_fastq_paired.argtypes = [vp, cp, cp, cp, cp, C.POINTER(CFilterParams), C.POINTER(CFilterParams), ip, C.c_int64,
                                                C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp, cp, C.c_size_t]
+    L.dada2hip_filter_reads_oriented.argtypes = [vp, C.c_int64, vp, vp, vp, C.POINTER(CFilterParams), cp, ip, vp, vp, vp, vp, vp, vp, vp, vp, cp,
+                                                 C.c_size_t]
+    L.dada2hip_filter_fastq_oriented.argtypes = [vp, cp, cp, C.POINTER(CFilterParams), cp, ip, C.c_int64, C.POINTER(C.c_int64),
+                                                 C.POINTER(C.c_int64), vp, cp, C.c_size_t]
+    L.dada2hip_filter_fastq_paired_ex.argtypes = [vp, cp, cp, cp, cp, C.POINTER(CFilterParams), C.POINTER(CFilterParams), cp, ip, cp, ip, ip,
+                                                  C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp, cp, C.c_size_t]
     L.dada2hip_primers_reads.argtypes = [C.c_int64, vp, vp, C.POINTER(CPrimerParams), ip, vp, vp, vp, vp, vp, vp, vp, cp, C.c_size_t]
     L.dada2hip_primers_fastq.argtypes = [cp, cp, C.POINTER(CPrimerParams), ip, C.c_int64, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                          vp, cp, C.c_size_t]

@@ -1537,13 +1537,15 @@ def fastq_paired_filter(fn, fout, *, compress=True, n=10**6, quality_type=0, ver
 
 def filter_and_trim(fwd, filt, rev=None, filt_rev=None, *, compress=True, trunc_q=2, trunc_len=0, trim_left=0, trim_right=0,
                     max_len=float("inf"), min_len=20, max_n=0, min_q=0, max_ee=float("inf"), rm_phix=False, rm_lowcomplex=0, n=10**5,
-                    quality_type=0, device: int = 0, verbose=False, ctx: FilterContext = None, **kw):
+                    quality_type=0, device: int = 0, verbose=False, ctx: FilterContext = None, _per_file=None, **kw):
     """filterAndTrim (R/filter.R:402-497) over one file or lists of files: returns (an (nfiles, 2) int64 array of reads.in /
     reads.out, the row names basename(fwd)).  ``rm_phix``: the phiX genome as a sequence or the path of a FASTA file (the library
     ships no copy), or False.  Output directories are created; duplicate output paths and outputs equal to an input are
-    refused; a file from which nothing passes is not written."""
+    refused; a file from which nothing passes is not written.  ``_per_file``: the (single-end, paired) functions run per file, for
+    modules that wrap this one; by default fastq_filter and fastq_paired_filter."""
     import os
     _refuse_filter_args(kw)
+    single, pair = _per_file or (fastq_filter, fastq_paired_filter)
     aslist = lambda x: [os.fspath(x)] if (isinstance(x, (str, bytes)) or hasattr(x, "__fspath__")) else [os.fspath(y) for y in x]   # noqa: E731
     fwd, filt = aslist(fwd), aslist(filt)
     if not all(os.path.exists(f) for f in fwd):
@@ -1582,11 +1584,11 @@ def filter_and_trim(fwd, filt, rev=None, filt_rev=None, *, compress=True, trunc_
     try:
         for i in range(len(fwd)):
             if paired:
-                rval[i] = fastq_paired_filter((fwd[i], rev[i]), (filt[i], filt_rev[i]), compress=compress, n=n, quality_type=quality_type,
-                                              verbose=verbose, rm_phix=bool(rm_phix), ctx=c, **args)
+                rval[i] = pair((fwd[i], rev[i]), (filt[i], filt_rev[i]), compress=compress, n=n, quality_type=quality_type,
+                               verbose=verbose, rm_phix=bool(rm_phix), ctx=c, **args)
             else:
-                rval[i] = fastq_filter(fwd[i], filt[i], compress=compress, n=n, quality_type=quality_type, verbose=verbose,
-                                       rm_phix=bool(rm_phix), ctx=c, **args)
+                rval[i] = single(fwd[i], filt[i], compress=compress, n=n, quality_type=quality_type, verbose=verbose,
+                                 rm_phix=bool(rm_phix), ctx=c, **args)
     finally:
         if own:
             c.close()

@@ -735,6 +735,7 @@ extern "C" int dada2hip_derep_combine(int32_t nsamples, const dada2hip_derep_vie
 // its own (concatenated members are one valid .gz; a single deflate stream on one thread would be the whole run).
 #include <sys/stat.h>
 
+#include "filter_ids_plain.h"
 #include "readqc_plain.h"
 #include "stage_stats.h"
 
@@ -1037,6 +1038,249 @@ int filter_files_body(dada2hip_filter *ctx, int nfile, const char *const *in, co
   return rc != DADA2HIP_OK ? rc : call.finish(tot, sizeof tot, FS_US_TOTAL, stats);
 }
 
+// ---- orient.fwd, matchIDs, id.sep, id.field (R/filter.R:648-658, :940-1007) ---------------------------------------------------------
+// dada2hip_filter_fastq_oriented and dada2hip_filter_fastq_paired_ex have a chunk loop of their own: a chunk's output is two runs
+// of records (the reads as given, then the flipped or swapped ones), a pair's records can change files, and matchIDs carries the
+// unmatched tail of each side into the next chunk.  fq_run_chunks and the entries above are not touched by any of it.
+// the records idx[0 .. m) of s behind those of d: the offsets first, then the bytes over the host pool
+void fq_gather(FqChunk &d, const FqChunk &s, const std::vector<int64_t> &idx) {
+  const size_t m = idx.size(), n0 = (size_t)d.n;
+  d.hoff.resize(n0 + m + 1); d.off.resize(n0 + m + 1);
+  for (size_t j = 0; j < m; j++) {
+    d.hoff[n0 + j + 1] = d.hoff[n0 + j] + (s.hoff[idx[j] + 1] - s.hoff[idx[j]]);
+    d.off[n0 + j + 1] = d.off[n0 + j] + (s.off[idx[j] + 1] - s.off[idx[j]]);
+  }
+  d.hdr.resize((size_t)d.hoff[n0 + m]); d.seq.resize((size_t)d.off[n0 + m]); d.qual.resize((size_t)d.off[n0 + m]);
+  d2::parallel_for(m, 2048, [&](size_t lo, size_t hi) {
+    for (size_t j = lo; j < hi; j++) {
+      const int64_t i = idx[j];
+      const size_t hl = (size_t)(s.hoff[i + 1] - s.hoff[i]), sl = (size_t)(s.off[i + 1] - s.off[i]);
+      if (hl) memcpy(d.hdr.data() + d.hoff[n0 + j], s.hdr.data() + s.hoff[i], hl);
+      if (sl) {
+        memcpy(d.seq.data() + d.off[n0 + j], s.seq.data() + s.off[i], sl);
+        memcpy(d.qual.data() + d.off[n0 + j], s.qual.data() + s.off[i], sl);
+      }
+    }
+  });
+  d.n += (int64_t)m;
+}
+// idx = the i in [lo, hi) with pick(i)
+template <typename Pick> const std::vector<int64_t> &fq_pick(std::vector<int64_t> &idx, int64_t lo, int64_t hi, Pick &&pick) {
+  idx.clear();
+  for (int64_t i = lo; i < hi; i++) if (pick(i)) idx.push_back(i);
+  return idx;
+}
+std::string fq_id(const FqChunk &c, int64_t i) { return std::string(c.hdr.data() + c.hoff[i], (size_t)(c.hoff[i + 1] - c.hoff[i])); }
+
+int filter_files_ex_body(dada2hip_filter *ctx, int nfile, const char *const *in, const char *const *out,
+                         const dada2hip_filter_params *const *params, const char *orient_fwd, int32_t match_ids, const char *id_sep,
+                         int32_t id_field, int32_t compress, int64_t chunk_reads, int64_t *reads_in, int64_t *reads_out, int64_t *stats,
+                         char *errbuf, size_t errlen) {
+  FqCall call(reads_in, reads_out);
+  auto fail = [&](int code, const std::string &msg) { set_err(errbuf, errlen, msg.c_str()); return code; };
+  for (int k = 0; k < nfile; k++)
+    if (!in[k] || !out[k] || !params[k]) return fail(DADA2HIP_ERR_INPUT, "File paths must be provided in character format.");
+  for (int a = 0; a < nfile; a++) {                             // :627, :887
+    for (int b = 0; b < nfile; b++)
+      if (strcmp(in[a], out[b]) == 0)
+        return fail(DADA2HIP_ERR_INPUT, nfile == 1 ? "The output and input files must be different." : "The output and input file names must be different.");
+    for (int b = 0; b < a; b++)
+      if (strcmp(out[a], out[b]) == 0 || strcmp(in[a], in[b]) == 0) return fail(DADA2HIP_ERR_INPUT, "The output and input file names must be different.");
+  }
+  if (orient_fwd) {                                             // :650, :995 (the library checks again; an empty file reaches no call of it)
+    if (!*orient_fwd) return fail(DADA2HIP_ERR_INPUT, "dada2hip: orient_fwd is empty.");
+    for (const char *c = orient_fwd; *c; c++)
+      if (!strchr("ACGT", *c)) return fail(DADA2HIP_ERR_INPUT, "Non-ACGT characters detected in orient.fwd");
+  }
+  const bool match = nfile == 2 && match_ids != 0;              // (single-end: matchIDs is ignored, as in the reference)
+  fid::Sep sep;
+  if (match) {
+    if (id_sep && strcmp(id_sep, "\\s") != 0) {
+      if (strlen(id_sep) != 1) return fail(DADA2HIP_ERR_UNSUPPORTED, "dada2hip: id_sep must be \"\\\\s\" or one literal character.");
+      sep.space = false; sep.ch = id_sep[0];
+    }
+    if (id_field < 0) return fail(DADA2HIP_ERR_INPUT, "dada2hip: id_field must be at least 1 (0: detect it).");
+  }
+  dada2hip_filter_params P[2];
+  for (int k = 0; k < nfile; k++) P[k] = *params[k];
+  int64_t tot[DADA2HIP_FILTER_NSTATS] = {0}, st[DADA2HIP_FILTER_NSTATS];
+  int64_t &nin = call.nin, &nout = call.nout;
+  if (chunk_reads <= 0) chunk_reads = 100000;
+  d2::knobs_reload();
+  FqSource src[2];
+  FqWriter wr[2];
+  FqChunk chunks[2][2], work[2], rem[2], sel[2], comp[2], tmp;
+  std::string err;
+  for (int k = 0; k < nfile; k++) {
+    const auto t_open = fclk::now();
+    if (!src[k].open(in[k], err)) return fail(DADA2HIP_ERR_INPUT, err);
+    tot[FS_US_INFLATE] += us_since(t_open);
+    wr[k].path = out[k]; wr[k].compress = compress != 0;
+  }
+  for (int k = 0; k < nfile; k++) { (void)remove(out[k]); rem[k].clear(); }
+  // a call's words into the file's (stage_stats.h): `counts` with the verdict counts (the forward reads'), else the clocks alone
+  auto add_stats = [&](bool counts) {
+    const int w0 = counts ? 0 : FS_CLOCK_FIRST, w1 = counts ? FS_COUNT - 1 : FS_CLOCK_LAST;
+    for (int i = w0; i <= w1; i++)
+      if (i >= FS_TAKEN_FIRST && i <= FS_TAKEN_LAST) tot[i] = st[i]; else if (i != FS_US_TOTAL) tot[i] += st[i];
+    tot[FO_US_ORIENT] += st[FO_US_ORIENT];
+  };
+  // the message of a read shorter than orient_fwd names the record (ori: 3 at the read the call stopped at)
+  auto name_short = [&](const FqChunk &c, const std::vector<int8_t> &ori, const char *which, int64_t first_no) {
+    for (int64_t i = 0; i < c.n; i++)
+      if (ori[(size_t)i] == 3) {
+        const std::string no = first_no > 0 ? " " + std::to_string(first_no + i) : std::string();
+        set_err(errbuf, errlen, ("dada2hip: " + std::string(which) + "read" + no + " (" + fq_id(c, i) + ") is shorter than orient_fwd.").c_str());
+        return;
+      }
+  };
+  std::vector<int32_t> code[2], win[2];
+  std::vector<uint8_t> keep, keep2, flip;
+  std::vector<int8_t> ori[2];
+  std::vector<fid::Key> keys[2];
+  std::vector<int64_t> idx;
+  auto pool_for = [](size_t n, size_t grain, auto &&f) { d2::parallel_for(n, grain, f); };
+  std::vector<uint8_t> inset[2];
+  bool old_format = false, first = true;
+  int64_t matched = 0;
+  int rc = DADA2HIP_OK;
+  struct Parsed { bool ok; std::string err; int64_t us; };
+  auto parse = [&](int slot) {
+    const auto t_parse = fclk::now();
+    Parsed r{true, std::string(), 0};
+    for (int k = 0; k < nfile && r.ok; k++) r.ok = fq_read_chunk(src[k], chunk_reads, chunks[slot][k], r.err);
+    r.us = us_since(t_parse);
+    return r;
+  };
+  std::future<Parsed> ahead = std::async(std::launch::async, parse, 0);
+  for (int slot = 0; rc == DADA2HIP_OK; slot ^= 1, first = false) {
+    const Parsed got = ahead.get();
+    tot[FS_US_PARSE] += got.us;
+    if (!got.ok) { rc = fail(DADA2HIP_ERR_INPUT, got.err); break; }
+    FqChunk *ch = chunks[slot];
+    if (nfile == 2 && !match && ch[0].n != ch[1].n) {           // :966
+      rc = fail(DADA2HIP_ERR_INPUT, "Mismatched forward and reverse sequence files: " + std::to_string(ch[0].n) + ", " + std::to_string(ch[1].n) + ".");
+      break;
+    }
+    if (ch[0].n == 0 && (nfile == 1 || ch[1].n == 0)) break;    // :645, :936
+    ahead = std::async(std::launch::async, parse, slot ^ 1);
+    const int64_t first_no = match ? 0 : nin + 1;               // the number of the chunk's first record, where records keep theirs
+    nin += ch[0].n;                                             // :646, :938
+    if (first)
+      for (int k = 0; k < nfile; k++)
+        if (P[k].qual_offset == 0) P[k].qual_offset = fq_auto_offset(ch[k]);
+    const FqChunk *cur[2] = {&ch[0], &ch[1]};
+    if (match) {                                                // :940-991
+      const auto t_join = fclk::now();
+      if (first) {
+        if (ch[0].n == 0) { rc = fail(DADA2HIP_ERR_INPUT, "dada2hip: the forward file's first chunk is empty: no id to detect the id field from."); break; }
+        if (id_field == 0) {
+          const std::string id1 = fq_id(ch[0], 0);
+          id_field = fid::detect_field(std::string_view(id1).substr(1), sep, old_format);
+          if (id_field == 0) { rc = fail(DADA2HIP_ERR_INPUT, "Couldn't automatically detect the sequence identifier field in the fastq id string."); break; }
+        }
+      }
+      for (int k = 0; k < 2; k++) {
+        const FqChunk *w = &ch[k];
+        if (rem[k].n > 0) {                                     // :962-963
+          std::swap(work[k], rem[k]);
+          fq_gather(work[k], ch[k], fq_pick(idx, 0, ch[k].n, [](int64_t) { return true; }));
+          w = &work[k];
+        }
+        cur[k] = w;
+        keys[k].resize((size_t)w->n);
+        d2::parallel_for((size_t)w->n, 4096, [&](size_t lo, size_t hi) {
+          for (size_t i = lo; i < hi; i++)
+            keys[k][i] = fid::id_key(std::string_view(w->hdr.data() + w->hoff[i], (size_t)(w->hoff[i + 1] - w->hoff[i])), sep, id_field,
+                                     old_format && k == 0);
+        });
+      }
+      fid::join(keys[0], keys[1], inset[0], inset[1], pool_for);
+      for (int k = 0; k < 2; k++) {
+        const FqChunk &w = *cur[k];
+        sel[k].clear(); tmp.clear();
+        fq_gather(sel[k], w, fq_pick(idx, 0, w.n, [&](int64_t i) { return inset[k][(size_t)i] != 0; }));
+        fq_gather(tmp, w, fq_pick(idx, (int64_t)fid::past_last(inset[k]), w.n, [](int64_t) { return true; }));
+        std::swap(rem[k], tmp);
+      }
+      tot[FO_US_IDJOIN] += us_since(t_join);
+      if (sel[0].n != sel[1].n) {
+        rc = fail(DADA2HIP_ERR_INPUT, "dada2hip: id matching kept " + std::to_string(sel[0].n) + " forward and " + std::to_string(sel[1].n) +
+                                          " reverse records of a chunk (duplicate ids?).");
+        break;
+      }
+      cur[0] = &sel[0]; cur[1] = &sel[1];
+      matched += sel[0].n;
+      if (sel[0].n == 0) continue;
+    }
+    int64_t n = cur[0]->n;
+    if (orient_fwd && nfile == 1) {                             // :648-658
+      const FqChunk &c = *cur[0];
+      code[0].resize((size_t)n); win[0].resize(2 * (size_t)n); ori[0].assign((size_t)n, 0);
+      rc = dada2hip_filter_reads_oriented(ctx, n, c.seq.data(), c.qual.data(), c.off.data(), &P[0], orient_fwd, 0, code[0].data(), win[0].data(),
+                                          nullptr, nullptr, nullptr, nullptr, ori[0].data(), st, errbuf, errlen);
+      if (rc != DADA2HIP_OK) { name_short(c, ori[0], "", first_no); break; }
+      add_stats(true);
+      tot[FO_DROPPED_ORIENT] += st[FO_DROPPED_ORIENT]; tot[FO_FLIPPED] += st[FO_FLIPPED];
+      keep.assign((size_t)n, 0); keep2.assign((size_t)n, 0); flip.assign((size_t)n, 0);
+      for (int64_t i = 0; i < n; i++) {
+        if (code[0][(size_t)i] != 0) continue;
+        if (ori[0][(size_t)i] == 1) { keep2[(size_t)i] = 1; flip[(size_t)i] = 1; } else keep[(size_t)i] = 1;
+        nout++;
+      }
+      // :655-657 c(fq[keepF], fq.rc[keepR])
+      if (!wr[0].put(c, keep, win[0], std::vector<uint8_t>(), err) || !wr[0].put(c, keep2, win[0], flip, err)) rc = fail(DADA2HIP_ERR_RUNTIME, err);
+      continue;
+    }
+    if (orient_fwd) {                                           // :993-1007: the forward test on both files, then the chunks rebuilt
+      for (int k = 0; k < 2 && rc == DADA2HIP_OK; k++) {
+        const FqChunk &c = *cur[k];
+        ori[k].assign((size_t)n, 0);
+        rc = dada2hip_filter_reads_oriented(ctx, n, c.seq.data(), nullptr, c.off.data(), nullptr, orient_fwd, 1, nullptr, nullptr, nullptr, nullptr,
+                                            nullptr, nullptr, ori[k].data(), st, errbuf, errlen);
+        if (rc != DADA2HIP_OK) { name_short(c, ori[k], k == 0 ? "forward " : "reverse ", first_no); break; }
+        add_stats(false);
+      }
+      if (rc != DADA2HIP_OK) break;
+      comp[0].clear(); comp[1].clear();
+      fq_pick(idx, 0, n, [&](int64_t i) { return ori[0][(size_t)i] == 0; });                          // keepF
+      fq_gather(comp[0], *cur[0], idx); fq_gather(comp[1], *cur[1], idx);
+      const int64_t as_given = comp[0].n;
+      fq_pick(idx, 0, n, [&](int64_t i) { return ori[0][(size_t)i] != 0 && ori[1][(size_t)i] == 0; });   // keepR
+      fq_gather(comp[0], *cur[1], idx); fq_gather(comp[1], *cur[0], idx);
+      tot[FO_FLIPPED] += comp[0].n - as_given; tot[FO_DROPPED_ORIENT] += n - comp[0].n;
+      cur[0] = &comp[0]; cur[1] = &comp[1];
+      n = comp[0].n;
+      if (n == 0) continue;
+    }
+    keep.assign((size_t)n, 1);
+    for (int k = 0; k < nfile; k++) {                           // as filter_files_body: each read by its direction's parameters, the pair's AND
+      const FqChunk &c = *cur[k];
+      code[k].resize((size_t)n); win[k].resize(2 * (size_t)n);
+      rc = dada2hip_filter_reads(ctx, n, c.seq.data(), c.qual.data(), c.off.data(), &P[k], code[k].data(), win[k].data(), nullptr, nullptr,
+                                 nullptr, nullptr, st, errbuf, errlen);
+      if (rc != DADA2HIP_OK) break;
+      add_stats(k == 0);
+      for (int64_t i = 0; i < n; i++) if (code[k][(size_t)i] != 0) keep[(size_t)i] = 0;
+    }
+    if (rc != DADA2HIP_OK) break;
+    for (int64_t i = 0; i < n; i++) nout += keep[(size_t)i];
+    for (int k = 0; k < nfile && rc == DADA2HIP_OK; k++)
+      if (!wr[k].put(*cur[k], keep, win[k], std::vector<uint8_t>(), err)) rc = fail(DADA2HIP_ERR_RUNTIME, err);
+  }
+  if (ahead.valid()) ahead.wait();
+  for (int k = 0; k < nfile; k++) {
+    if (!wr[k].finish(err) && rc == DADA2HIP_OK) rc = fail(DADA2HIP_ERR_RUNTIME, err);
+    tot[FS_US_DEFLATE] += wr[k].us_deflate; tot[FS_US_WRITE] += wr[k].us_write;
+  }
+  if (rc != DADA2HIP_OK) {                                      // nothing half written is left behind
+    for (int k = 0; k < nfile; k++) (void)remove(out[k]);
+    return rc;
+  }
+  if (match) tot[FO_DROPPED_IDS] = nin - matched;
+  return call.finish(tot, sizeof tot, FS_US_TOTAL, stats);
+}
+
 // removePrimers' file level (R/filter.R:116-225): dada2hip_primers_reads per chunk, the kept windows written in the kept
 // orientation, and the whole-file rule (:157-158) at the end - it asks for the matches of the reads AS GIVEN, summed over the file
 int primers_file_body(const char *in, const char *out, const dada2hip_primer_params *params, int32_t compress, int64_t chunk_reads,
@@ -1220,6 +1464,28 @@ int dada2hip_filter_fastq_paired(dada2hip_filter *ctx, const char *in_f, const c
   const dada2hip_filter_params *params[2] = {params_f, params_r};
   return filter_files_guarded(errbuf, errlen, [&] {
     return filter_files_body(ctx, 2, in, out, params, compress, chunk_reads, reads_in, reads_out, stats, errbuf, errlen);
+  });
+}
+
+int dada2hip_filter_fastq_oriented(dada2hip_filter *ctx, const char *in, const char *out, const dada2hip_filter_params *params,
+                                   const char *orient_fwd, int32_t compress, int64_t chunk_reads, int64_t *reads_in, int64_t *reads_out,
+                                   int64_t *stats, char *errbuf, size_t errlen) {
+  return filter_files_guarded(errbuf, errlen, [&] {
+    if (!orient_fwd) { set_err(errbuf, errlen, "dada2hip: bad arguments"); return (int)DADA2HIP_ERR_INPUT; }
+    return filter_files_ex_body(ctx, 1, &in, &out, &params, orient_fwd, 0, nullptr, 0, compress, chunk_reads, reads_in, reads_out, stats, errbuf,
+                                errlen);
+  });
+}
+
+int dada2hip_filter_fastq_paired_ex(dada2hip_filter *ctx, const char *in_f, const char *in_r, const char *out_f, const char *out_r,
+                                    const dada2hip_filter_params *params_f, const dada2hip_filter_params *params_r, const char *orient_fwd,
+                                    int32_t match_ids, const char *id_sep, int32_t id_field, int32_t compress, int64_t chunk_reads,
+                                    int64_t *reads_in, int64_t *reads_out, int64_t *stats, char *errbuf, size_t errlen) {
+  const char *in[2] = {in_f, in_r}, *out[2] = {out_f, out_r};
+  const dada2hip_filter_params *params[2] = {params_f, params_r};
+  return filter_files_guarded(errbuf, errlen, [&] {
+    return filter_files_ex_body(ctx, 2, in, out, params, orient_fwd, match_ids, id_sep, id_field, compress, chunk_reads, reads_in, reads_out,
+                                stats, errbuf, errlen);
   });
 }
 

@@ -651,6 +651,26 @@ void launch_filter_ee(const FilterArgs &A, int n, const uint8_t *d_qual, const l
 // counts[r][4^k]: the k-mers of the kept window that are A/C/G/T only, first letter most significant (oligonucleotideFrequency's order)
 void launch_filter_kmers(int n, int k, const uint8_t *d_seq, const long long *d_off, const FilterOut *d_out, int32_t *d_counts,
                          hipStream_t st);
+// orient.fwd (R/filter.R:648-658, :993-1007).  k_filter_orient leaves a read's orientation in FilterOut::pad: 0 the read starts
+// with the barcode, 1 its reverse complement does (and the read itself does not), 2 neither, 3 the read is shorter than the
+// barcode (narrow() fails in the reference; the host names the read).  forward_only (the paired form): 0, 2 or 3.  The barcode
+// travels by value, beside its complement (the letter a flipped read has to show at its END for the barcode's letter i).
+constexpr int FT_ORIENT_MAX = 256;            // letters of orient.fwd
+constexpr int FT_CODE_ORIENT = 12;            // the code of a read that is dropped by orientation
+struct FilterBarcode {
+  uint8_t fwd[FT_ORIENT_MAX], comp[FT_ORIENT_MAX];
+  int len;
+};
+void launch_filter_orient(const FilterBarcode &B, int forward_only, int n, const uint8_t *d_seq, const long long *d_off,
+                          FilterOut *d_out, hipStream_t st);
+// the three kernels on the ORIENTED read: where pad is 1, position p of the read is its letter L - 1 - p complemented (and its
+// quality L - 1 - p); `off` then counts from the read's end.  pad 2 or 3: code 12, an empty window, nothing counted.
+void launch_filter_scan_oriented(const FilterTable &T, const FilterArgs &A, int n, const uint8_t *d_seq, const uint8_t *d_qual,
+                                 const long long *d_off, FilterOut *d_out, hipStream_t st);
+void launch_filter_ee_oriented(const FilterArgs &A, int n, const uint8_t *d_qual, const long long *d_off, const double *d_ee_tab,
+                               FilterOut *d_out, hipStream_t st);
+void launch_filter_kmers_oriented(int n, int k, const uint8_t *d_seq, const long long *d_off, const FilterOut *d_out, int32_t *d_counts,
+                                  hipStream_t st);
 // removePrimers (primers.inc.hip).  A batch is n reads: the bytes of read r are seq[off[r] .. off[r + 1]).  Four patterns are searched
 // in the read as given: 0 the forward primer, 1 the reverse primer, 2 and 3 the reverse complements of the two (a match of P on the
 // read's reverse complement at start st is a match of rc(P) on the read at n - L - st).  A pattern letter is a byte of plane

@@ -18,8 +18,13 @@
 //                   tells them apart.  Then stages 9 (ee <= maxEE, :692) and 10 (either count >= minMatches).
 //   k_filter_kmers  a block of one wave per read: the k-mer histogram of seqComplexity in LDS, integer counts out; the Shannon
 //                   number is the host's (libm's log and exp, in bin order).
+//   k_filter_orient orient.fwd (:648-658): a wave per read, the barcode against the read's first letters and its complement against
+//                   the read's last letters backwards, 64 letters per ballot; one byte per read into FilterOut::pad.  The three
+//                   kernels above have an ORIENT instance each that reads it and traverses a flipped read from its end, letters
+//                   complemented; the instances without it are what the un-oriented entries launch, unchanged.
 // Codes: 0 kept, 1 maxLen, 2 trimLeft, 3 trimRight, 4 truncQ left nothing, 5 truncLen, 6 minLen, 7 maxN, 8 minQ, 9 maxEE, 10 phiX
-// (11, the complexity, is the host's).  A read that fails a stage 1-6 reports an empty window and no counts.
+// (11, the complexity, is the host's; 12, the oriented instances only: in neither orientation).  A read that fails a stage 1-6
+// reports an empty window and no counts.
 
 __device__ __forceinline__ int ft_code(uint8_t c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4; }
 
@@ -54,7 +59,10 @@ __device__ __forceinline__ void ft_count(unsigned long long m, int p0, int step,
   }
 }
 
-template <bool LDS>
+// ORIENT: the instance for dada2hip_filter_reads_oriented.  out[r].pad holds k_filter_orient's verdict, the same on every lane of the
+// read's wave; position p of a flipped read is letter L - 1 - p with its 2-bit code complemented (3 - code; "other" stays other), so
+// the truncQ ballot, the planes, the window keys and the greedy walk are those of the reverse complement read from ITS left end.
+template <bool LDS, bool ORIENT>
 __global__ __launch_bounds__(FT_THREADS) void k_filter_scan(FilterTable T, FilterArgs A, int n, const uint8_t *__restrict__ seq,
                                                              const uint8_t *__restrict__ qual, const long long *__restrict__ off,
                                                              FilterOut *__restrict__ out) {
@@ -77,7 +85,10 @@ __global__ __launch_bounds__(FT_THREADS) void k_filter_scan(FilterTable T, Filte
     const long long b = off[r];
     const int L = (int)(off[r + 1] - b);
     int code = 0, w = 0;
-    if (A.max_len > 0 && L > A.max_len) code = 1;              // :660
+    const int ori = ORIENT ? out[r].pad : 0;
+    const bool flip = ORIENT && ori == 1;
+    if (ORIENT && ori >= 2) code = FT_CODE_ORIENT;             // :655-657: in neither set
+    else if (A.max_len > 0 && L > A.max_len) code = 1;         // :660
     else if (L < A.skip + 1) code = 2;                         // :662
     else {
       w = L - A.skip;                                          // :663
@@ -86,10 +97,17 @@ __global__ __launch_bounds__(FT_THREADS) void k_filter_scan(FilterTable T, Filte
       }
     }
     const uint8_t *s = seq + b + A.skip, *q = qual + b + A.skip;
+    const uint8_t *se = seq + b + L - 1 - A.skip, *qe = qual + b + L - 1 - A.skip;   // (flipped: position p is se[-p], p < w <= L - skip)
+    auto qv = [&](int p) -> int { return flip ? (int)qe[-p] : (int)q[p]; };
+    auto cdv = [&](int p) -> int {
+      if (!flip) return ft_code(s[p]);
+      const int c = ft_code(se[-p]);
+      return c < 4 ? 3 - c : 4;
+    };
     if (code == 0) {                                           // :677, then the reads left with nothing
       for (int p0 = 0; p0 < w; p0 += 64) {
         const int p = p0 + lane;
-        const unsigned long long m = __ballot(p < w && (int)q[p] <= A.cut_char);
+        const unsigned long long m = __ballot(p < w && qv(p) <= A.cut_char);
         if (m != 0ull) { w = p0 + __builtin_ctzll(m); break; }
       }
       if (w == 0) code = 4;
@@ -108,8 +126,8 @@ __global__ __launch_bounds__(FT_THREADS) void k_filter_scan(FilterTable T, Filte
         const int p = p0 + 64 + lane;
         int cd = 0;
         if (p < w) {
-          cd = ft_code(s[p]);
-          mq = min(mq, (int)q[p]);
+          cd = cdv(p);
+          mq = min(mq, qv(p));
         }
         n0 = __ballot(cd & 1); n1 = __ballot(cd & 2); nn = __ballot(cd & 4);
         nother += __popcll(nn);
@@ -131,13 +149,14 @@ __global__ __launch_bounds__(FT_THREADS) void k_filter_scan(FilterTable T, Filte
     }
     if (lane == 0) {
       FilterOut o;
-      o.code = code; o.off = A.skip; o.len = (code >= 1 && code <= 6) ? 0 : w; o.nother = nother; o.minq = mq; o.hits_f = hf; o.hits_r = hr;
-      o.pad = 0; o.ee = 0.0;
+      o.code = code; o.off = A.skip; o.len = ((code >= 1 && code <= 6) || (ORIENT && code == FT_CODE_ORIENT)) ? 0 : w; o.nother = nother; o.minq = mq; o.hits_f = hf; o.hits_r = hr;
+      o.pad = ori; o.ee = 0.0;
       out[r] = o;
     }
   }
 }
 
+template <bool ORIENT>
 __global__ __launch_bounds__(256) void k_filter_ee(FilterArgs A, int n, const uint8_t *__restrict__ qual, const long long *__restrict__ off,
                                                    const double *__restrict__ ee_tab, FilterOut *__restrict__ out) {
   __shared__ double s_tab[256];
@@ -150,6 +169,10 @@ __global__ __launch_bounds__(256) void k_filter_ee(FilterArgs A, int n, const ui
   if (len <= 0) return;
   const uint8_t *q = qual + off[r] + out[r].off;
   double ee = 0.0;
+  if (ORIENT && out[r].pad == 1) {                             // the reverse complement's qualities, in ITS order
+    const uint8_t *qe = qual + off[r + 1] - 1 - out[r].off;
+    for (int j = 0; j < len; j++) ee += s_tab[qe[-j]];
+  } else
   for (int j = 0; j < len; j++) ee += s_tab[q[j]];             // src/filter.cpp:41-45, in this order
   out[r].ee = ee;
   if (code == 0) {
@@ -160,6 +183,7 @@ __global__ __launch_bounds__(256) void k_filter_ee(FilterArgs A, int n, const ui
 }
 
 // a block of 64 threads per read; 4^k <= 256 bins
+template <bool ORIENT>
 __global__ __launch_bounds__(64) void k_filter_kmers(int n, int k, const uint8_t *__restrict__ seq, const long long *__restrict__ off,
                                                      const FilterOut *__restrict__ out, int32_t *__restrict__ counts) {
   __shared__ int32_t s_h[256];
@@ -169,10 +193,13 @@ __global__ __launch_bounds__(64) void k_filter_kmers(int n, int k, const uint8_t
     __syncthreads();
     const int len = out[r].len;
     const uint8_t *s = seq + off[r] + out[r].off;
+    const bool flip = ORIENT && out[r].pad == 1;
+    const uint8_t *se = seq + off[r + 1] - 1 - out[r].off;
     for (int p = (int)threadIdx.x; p + k <= len; p += 64) {
       int idx = 0, bad = 0;
       for (int t = 0; t < k; t++) {
-        const int cd = ft_code(s[p + t]);
+        int cd = ft_code(flip ? se[-(p + t)] : s[p + t]);
+        if (flip && cd < 4) cd = 3 - cd;
         bad |= cd & 4;
         idx = idx * 4 + (cd & 3);
       }
@@ -184,31 +211,79 @@ __global__ __launch_bounds__(64) void k_filter_kmers(int n, int k, const uint8_t
   }
 }
 
-void launch_filter_scan(const FilterTable &T, const FilterArgs &A, int n, const uint8_t *d_seq, const uint8_t *d_qual,
-                        const long long *d_off, FilterOut *d_out, hipStream_t st) {
+// orient.fwd: a wave per read; the barcode against the read's first letters and (unless forward_only) its complement against the
+// read's last letters read backwards, 64 letters per ballot
+__global__ __launch_bounds__(256) void k_filter_orient(FilterBarcode B, int forward_only, int n, const uint8_t *__restrict__ seq,
+                                                       const long long *__restrict__ off, FilterOut *__restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), nwaves = (int)((gridDim.x * blockDim.x) >> 6);
+  for (int r = wave; r < n; r += nwaves) {
+    const long long b = off[r];
+    const int L = (int)(off[r + 1] - b);
+    int flag = 3;                                              // narrow(x, 1, barlen) on a shorter read
+    if (L >= B.len) {
+      bool bad_f = false, bad_r = forward_only != 0;
+      for (int c0 = 0; c0 < B.len && !(bad_f && bad_r); c0 += 64) {
+        const int i = c0 + lane;
+        const bool in = i < B.len;
+        if (!bad_f) bad_f = __ballot(in && seq[b + i] != B.fwd[i]) != 0ull;            // :653
+        if (!bad_r) bad_r = __ballot(in && seq[b + L - 1 - i] != B.comp[i]) != 0ull;   // :652, :654
+      }
+      flag = !bad_f ? 0 : !bad_r ? 1 : 2;                      // :654 `& !keepF`: both ends match -> as given
+    }
+    if (lane == 0) out[r].pad = flag;
+  }
+}
+
+template <bool ORIENT>
+void launch_filter_scan_t(const FilterTable &T, const FilterArgs &A, int n, const uint8_t *d_seq, const uint8_t *d_qual,
+                          const long long *d_off, FilterOut *d_out, hipStream_t st) {
   if (n <= 0) return;
   const unsigned grid = (unsigned)std::min((n + FT_THREADS / 64 - 1) / (FT_THREADS / 64), 512);
   const size_t lds = (size_t)T.nkeys * 9 + 8;
   if (T.nkeys > 0 && lds <= (size_t)FT_LDS_MAX) {
     // (more than 64 KiB of dynamic LDS has to be asked for, per device; a part that refuses searches global memory)
     if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void *)k_filter_scan<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        hipFuncSetAttribute((const void *)k_filter_scan<true, ORIENT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
       (void)hipGetLastError();
-      hipLaunchKernelGGL(k_filter_scan<false>, dim3(grid), dim3(FT_THREADS), 0, st, T, A, n, d_seq, d_qual, d_off, d_out);
+      hipLaunchKernelGGL((k_filter_scan<false, ORIENT>), dim3(grid), dim3(FT_THREADS), 0, st, T, A, n, d_seq, d_qual, d_off, d_out);
       return;
     }
-    hipLaunchKernelGGL(k_filter_scan<true>, dim3(grid), dim3(FT_THREADS), lds, st, T, A, n, d_seq, d_qual, d_off, d_out);
+    hipLaunchKernelGGL((k_filter_scan<true, ORIENT>), dim3(grid), dim3(FT_THREADS), lds, st, T, A, n, d_seq, d_qual, d_off, d_out);
   } else {
-    hipLaunchKernelGGL(k_filter_scan<false>, dim3(grid), dim3(FT_THREADS), 0, st, T, A, n, d_seq, d_qual, d_off, d_out);
+    hipLaunchKernelGGL((k_filter_scan<false, ORIENT>), dim3(grid), dim3(FT_THREADS), 0, st, T, A, n, d_seq, d_qual, d_off, d_out);
   }
+}
+void launch_filter_scan(const FilterTable &T, const FilterArgs &A, int n, const uint8_t *d_seq, const uint8_t *d_qual,
+                        const long long *d_off, FilterOut *d_out, hipStream_t st) {
+  launch_filter_scan_t<false>(T, A, n, d_seq, d_qual, d_off, d_out, st);
+}
+void launch_filter_scan_oriented(const FilterTable &T, const FilterArgs &A, int n, const uint8_t *d_seq, const uint8_t *d_qual,
+                                 const long long *d_off, FilterOut *d_out, hipStream_t st) {
+  launch_filter_scan_t<true>(T, A, n, d_seq, d_qual, d_off, d_out, st);
 }
 void launch_filter_ee(const FilterArgs &A, int n, const uint8_t *d_qual, const long long *d_off, const double *d_ee_tab, FilterOut *d_out,
                       hipStream_t st) {
   if (n <= 0) return;
-  hipLaunchKernelGGL(k_filter_ee, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A, n, d_qual, d_off, d_ee_tab, d_out);
+  hipLaunchKernelGGL(k_filter_ee<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A, n, d_qual, d_off, d_ee_tab, d_out);
+}
+void launch_filter_ee_oriented(const FilterArgs &A, int n, const uint8_t *d_qual, const long long *d_off, const double *d_ee_tab,
+                               FilterOut *d_out, hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_filter_ee<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A, n, d_qual, d_off, d_ee_tab, d_out);
 }
 void launch_filter_kmers(int n, int k, const uint8_t *d_seq, const long long *d_off, const FilterOut *d_out, int32_t *d_counts,
                          hipStream_t st) {
   if (n <= 0) return;
-  hipLaunchKernelGGL(k_filter_kmers, dim3((unsigned)std::min(n, 16384)), dim3(64), 0, st, n, k, d_seq, d_off, d_out, d_counts);
+  hipLaunchKernelGGL(k_filter_kmers<false>, dim3((unsigned)std::min(n, 16384)), dim3(64), 0, st, n, k, d_seq, d_off, d_out, d_counts);
+}
+void launch_filter_kmers_oriented(int n, int k, const uint8_t *d_seq, const long long *d_off, const FilterOut *d_out, int32_t *d_counts,
+                                  hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_filter_kmers<true>, dim3((unsigned)std::min(n, 16384)), dim3(64), 0, st, n, k, d_seq, d_off, d_out, d_counts);
+}
+void launch_filter_orient(const FilterBarcode &B, int forward_only, int n, const uint8_t *d_seq, const long long *d_off, FilterOut *d_out,
+                          hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_filter_orient, dim3((unsigned)std::min((n + 3) / 4, 4096)), dim3(256), 0, st, B, forward_only, n, d_seq, d_off, d_out);
 }

@@ -9,7 +9,8 @@
 // dada2hip_filter_reads takes sequences and qualities up through read_pieces.h's two-slot pipeline (DADA2HIP_FILTER_PIECE,
 // DADA2HIP_FILTER_PIECE_BYTES: smaller pieces, for the tests), the slots kept in the context, and supplies the three kernels
 // between four events and the scatter, where the Shannon number of seqComplexity (:1271-1275) is computed from the device's
-// integer counts.  From stage_common.h: the A/C/G/T code, the reverse complement, the clocks, the end of a call.
+// integer counts.  dada2hip_filter_reads_oriented (orient.fwd, R/filter.R:648-658) is the same body with k_filter_orient in front
+// and the kernels' oriented instances behind it; its stats words follow the filter's (FO_*, stage_stats.h).  From stage_common.h: the A/C/G/T code, the reverse complement, the clocks, the end of a call.
 #pragma once
 
 struct dada2hip_filter {
@@ -20,6 +21,7 @@ struct dada2hip_filter {
   DevBuf<uint8_t> flags;
   DevBuf<double> ee_tab;               // [2][256]: offset 33, offset 64
   PieceSlot<FilterOut, 4> slot[2];     // aux: the k-mer counts
+  Events<1> ev_orient[2];              // per slot, behind k_filter_orient (dada2hip_filter_reads_oriented)
   std::mutex mu;                       // calls on one context take turns (its slots and streams)
 };
 
@@ -81,6 +83,7 @@ void filter_open_body(const char *ref, int32_t word_size, int32_t device, dada2h
   m->device = device; m->word_size = ref ? word_size : 0; m->nkeys = (int)keys.size();
   m->in_lds = !keys.empty() && keys.size() * 9 + 8 <= (size_t)FT_LDS_MAX;
   for (FtSlot &S : m->slot) S.create();
+  for (auto &e : m->ev_orient) e.create();
   m->keys.alloc(keys.size()); m->flags.alloc(flags.size()); m->ee_tab.alloc(512);
   if (!keys.empty()) {
     D2_HIP(hipMemcpy(m->keys.p, keys.data(), keys.size() * 8, hipMemcpyHostToDevice));
@@ -93,13 +96,43 @@ void filter_open_body(const char *ref, int32_t word_size, int32_t device, dada2h
   *out = m.release();
 }
 
+// the barcode of orient.fwd as the kernel takes it (R/filter.R:650 C_isACGT, :651 barlen)
+FilterBarcode filter_barcode(const char *orient_fwd) {
+  FilterBarcode B;
+  memset(&B, 0, sizeof B);
+  const size_t len = strlen(orient_fwd);
+  if (len == 0) throw InputError{"dada2hip: orient_fwd is empty."};
+  if (len > (size_t)FT_ORIENT_MAX) throw RuntimeErr{DADA2HIP_ERR_UNSUPPORTED, "dada2hip: orient_fwd is longer than 256 letters."};
+  for (size_t i = 0; i < len; i++) {
+    const int c = acgt_code(orient_fwd[i]);
+    if (c < 0) throw InputError{"Non-ACGT characters detected in orient.fwd"};
+    B.fwd[i] = (uint8_t)orient_fwd[i];
+    B.comp[i] = (uint8_t)"TGCA"[c];
+  }
+  B.len = (int)len;
+  return B;
+}
+
+// orient_fwd == nullptr: dada2hip_filter_reads.  Otherwise dada2hip_filter_reads_oriented in orient_mode 0 (single-end: both tests,
+// a flipped read judged as its reverse complement) or 1 (the paired form: the forward test alone and nothing else - the caller
+// rebuilds its chunks from the verdicts of both files before anything is judged)
 void filter_reads_body(dada2hip_filter *m, int64_t n, const char *seq, const char *qual, const int64_t *offsets,
                        const dada2hip_filter_params *P, int32_t *code, int32_t *window, double *ee, int32_t *hits, int32_t *kmer_counts,
-                       double *complexity, int64_t *stats) {
+                       double *complexity, int64_t *stats, const char *orient_fwd = nullptr, int32_t orient_mode = 0,
+                       int8_t *orient = nullptr) {
   auto t_call = clk::now();
   int64_t st[DADA2HIP_FILTER_NSTATS] = {0};
   if (!m) throw InputError{"dada2hip: no filter context."};
-  if (!P || n < 0 || (n > 0 && (!seq || !qual || !offsets))) throw InputError{"dada2hip: bad arguments"};
+  const bool ori = orient_fwd != nullptr, only = ori && orient_mode == 1;
+  if (ori && orient_mode != 0 && orient_mode != 1) throw InputError{"dada2hip: bad arguments"};
+  FilterBarcode B;
+  if (ori) B = filter_barcode(orient_fwd);
+  if (only) {
+    if (n < 0 || (n > 0 && (!seq || !offsets))) throw InputError{"dada2hip: bad arguments"};
+    static const dada2hip_filter_params none = {-1, 0, 0, 0, 0, 0, INT32_MAX, 0, HUGE_VAL, 0.0, 0, 2, 1, 0, 33, 0};
+    P = &none; qual = nullptr; ee = nullptr; hits = nullptr; kmer_counts = nullptr; complexity = nullptr;
+  }
+  if (!P || n < 0 || (n > 0 && (!seq || (!qual && !only) || !offsets))) throw InputError{"dada2hip: bad arguments"};
   if (P->qual_offset != 0 && P->qual_offset != 33 && P->qual_offset != 64) throw InputError{"dada2hip: the quality offset must be 33, 64 or 0 (Auto)."};
   if (P->kmer_size < 0 || P->kmer_size > 4) throw RuntimeErr{DADA2HIP_ERR_UNSUPPORTED, "dada2hip: seqComplexity's kmerSize must be 1..4."};
   if (P->rm_phix && m->nkeys == 0) throw InputError{"dada2hip: rm_phix needs a context opened with the screen's reference sequence."};
@@ -112,7 +145,7 @@ void filter_reads_body(dada2hip_filter *m, int64_t n, const char *seq, const cha
   }
   st[FS_IN] = n; st[FS_KEYS] = m->nkeys; st[FS_LDS] = m->in_lds ? 1 : 0;
   int offset = P->qual_offset;
-  if (offset == 0) {                                           // Auto, as dada2hip_derep_fastq: below ';' only Phred+33 encodings
+  if (offset == 0 && !only) {                                  // Auto, as dada2hip_derep_fastq: below ';' only Phred+33 encodings
     const size_t b0 = n ? (size_t)offsets[0] : 0, b1 = n ? (size_t)offsets[n] : 0;
     std::atomic<int> mn{255};
     parallel_for(b1 - b0, (size_t)1 << 20, [&](size_t lo, size_t hi) {
@@ -138,6 +171,18 @@ void filter_reads_body(dada2hip_filter *m, int64_t n, const char *seq, const cha
   const double *d_tab = m->ee_tab.p + (offset == 64 ? 256 : 0);
   // ---- the stage's part of the pipeline: three kernels between four events; the scatter ----
   auto launch = [&](FtSlot &S, int c) {
+    if (ori) {
+      hipEvent_t e_or = m->ev_orient[&S - m->slot][0];
+      launch_filter_orient(B, only ? 1 : 0, c, S.d_seq.p, S.d_off.p, S.d_out.p, S.st);
+      D2_HIP(hipEventRecord(e_or, S.st));
+      if (only) return;
+      launch_filter_scan_oriented(T, A, c, S.d_seq.p, S.d_qual.p, S.d_off.p, S.d_out.p, S.st);
+      D2_HIP(hipEventRecord(S.ev[1], S.st));
+      launch_filter_ee_oriented(A, c, S.d_qual.p, S.d_off.p, d_tab, S.d_out.p, S.st);
+      D2_HIP(hipEventRecord(S.ev[2], S.st));
+      if (want_km) launch_filter_kmers_oriented(c, k, S.d_seq.p, S.d_off.p, S.d_out.p, S.d_aux.p, S.st);
+      return;
+    }
     launch_filter_scan(T, A, c, S.d_seq.p, S.d_qual.p, S.d_off.p, S.d_out.p, S.st);
     D2_HIP(hipEventRecord(S.ev[1], S.st));
     launch_filter_ee(A, c, S.d_qual.p, S.d_off.p, d_tab, S.d_out.p, S.st);
@@ -145,16 +190,41 @@ void filter_reads_body(dada2hip_filter *m, int64_t n, const char *seq, const cha
     if (want_km) launch_filter_kmers(c, k, S.d_seq.p, S.d_off.p, S.d_out.p, S.d_aux.p, S.st);
   };
   auto scatter = [&](FtSlot &S) {
+    const int64_t f = S.first, c = S.count;
+    const FilterOut *o = S.h_out.p;
+    if (ori) {
+      hipEvent_t e_or = m->ev_orient[&S - m->slot][0];
+      add_elapsed(st[FO_US_ORIENT], S.ev[0], e_or);
+      int64_t nflip = 0, nshort = 0, first_short = -1;
+      for (int64_t i = 0; i < c; i++) {
+        const int v = o[i].pad;
+        if (orient) orient[f + i] = (int8_t)v;
+        nflip += v == 1;
+        if (v == 3 && nshort++ == 0) first_short = f + i;
+      }
+      st[FO_FLIPPED] += nflip;
+      if (nshort) throw InputError{"dada2hip: read " + std::to_string(first_short + 1) + " is shorter than orient_fwd."};
+      if (only) {
+        int64_t drop = 0;
+        for (int64_t i = 0; i < c; i++) {
+          const int cd = o[i].pad == 0 ? 0 : FT_CODE_ORIENT;
+          if (code) code[f + i] = cd;
+          if (window) { window[2 * (f + i)] = 0; window[2 * (f + i) + 1] = 0; }
+          drop += cd != 0;
+        }
+        st[FO_DROPPED_ORIENT] += drop; st[FS_KEPT] += c - drop;
+        return;
+      }
+      add_elapsed(st[FS_US_SCAN], e_or, S.ev[1]);
+    } else
     add_elapsed(st[FS_US_SCAN], S.ev[0], S.ev[1]);
     add_elapsed(st[FS_US_EE], S.ev[1], S.ev[2]);
     add_elapsed(st[FS_US_KMERS], S.ev[2], S.ev[3]);
-    const int64_t f = S.first, c = S.count;
-    const FilterOut *o = S.h_out.p;
     const int32_t *km = S.h_aux.p;
-    int64_t dropped[12] = {0};
+    int64_t dropped[13] = {0};
     std::mutex cmu;
     parallel_for((size_t)c, 4096, [&](size_t lo, size_t hi) {
-      int64_t loc[12] = {0};
+      int64_t loc[13] = {0};
       for (size_t i = lo; i < hi; i++) {
         int cd = o[i].code;
         double cx = 0.0;
@@ -179,12 +249,13 @@ void filter_reads_body(dada2hip_filter *m, int64_t n, const char *seq, const cha
         loc[cd]++;
       }
       std::lock_guard<std::mutex> g(cmu);
-      for (int s = 0; s < 12; s++) dropped[s] += loc[s];
+      for (int s = 0; s < 13; s++) dropped[s] += loc[s];
     });
     st[FS_KEPT] += dropped[0];
     for (int s = 1; s < 12; s++) st[FS_STAGE1 + s - 1] += dropped[s];
+    st[FO_DROPPED_ORIENT] += dropped[FT_CODE_ORIENT];
   };
-  run_pieces(m->slot, n, seq, qual, offsets, knobs().filter_piece, knobs().filter_piece_bytes, want_km ? (size_t)nb : 0, st, FS_BYTES,
+  run_pieces(m->slot, n, seq, only ? nullptr : qual, offsets, knobs().filter_piece, knobs().filter_piece_bytes, want_km ? (size_t)nb : 0, st, FS_BYTES,
              FS_US_UP, FS_US_DOWN, launch, scatter);
   finish_stats(st, FS_US_TOTAL, t_call, stats);
 }
@@ -203,4 +274,15 @@ int dada2hip_filter_reads(dada2hip_filter *ctx, int64_t n, const char *seq, cons
                           int32_t *kmer_counts, double *complexity, int64_t *stats, char *errbuf, size_t errlen) {
   return guarded(errbuf, errlen,
                  [&] { filter_reads_body(ctx, n, seq, qual, offsets, params, code, window, ee, hits, kmer_counts, complexity, stats); });
+}
+
+int dada2hip_filter_reads_oriented(dada2hip_filter *ctx, int64_t n, const char *seq, const char *qual, const int64_t *offsets,
+                                   const dada2hip_filter_params *params, const char *orient_fwd, int32_t orient_mode, int32_t *code,
+                                   int32_t *window, double *ee, int32_t *hits, int32_t *kmer_counts, double *complexity, int8_t *orient,
+                                   int64_t *stats, char *errbuf, size_t errlen) {
+  return guarded(errbuf, errlen, [&] {
+    if (!orient_fwd) throw InputError{"dada2hip: bad arguments"};
+    filter_reads_body(ctx, n, seq, qual, offsets, params, code, window, ee, hits, kmer_counts, complexity, stats, orient_fwd, orient_mode,
+                      orient);
+  });
 }

@@ -14,6 +14,10 @@ enum { SS_REFS = 0, SS_BASES, SS_WINDOWS, SS_PAST_BITMAP, SS_CANDIDATES, SS_RERU
 // FS_STAGE1 .. + 10: the reads dropped at stage 1..11; PS_CODE1 .. + 3: those with code 1..4.  *_US_PARSE and behind: the file level's.
 enum { FS_IN = 0, FS_KEPT, FS_STAGE1, FS_KEYS = 13, FS_LDS, FS_BYTES, FS_US_UP, FS_US_SCAN, FS_US_EE, FS_US_KMERS, FS_US_DOWN, FS_US_PARSE,
        FS_US_DEFLATE, FS_US_WRITE, FS_US_TOTAL, FS_US_INFLATE, FS_COUNT };
+// the words of the oriented / id-matching entries, behind the filter's: reads (pairs) in neither orientation, reads flipped (pairs
+// swapped), forward records that found no partner by id, device microseconds of k_filter_orient, host microseconds of the id join
+enum { FO_DROPPED_ORIENT = FS_COUNT, FO_FLIPPED, FO_DROPPED_IDS, FO_US_ORIENT, FO_US_IDJOIN, FO_COUNT };
+static_assert(FS_COUNT == 26 && FO_COUNT <= DADA2HIP_FILTER_NSTATS, "stats words");
 enum { PS_IN = 0, PS_KEPT, PS_CODE1, PS_FLIPPED = 6, PS_MULTI, PS_HITS_FWD, PS_HITS_REV, PS_PIECES, PS_TILES, PS_BYTES, PS_US_UP, PS_US_KERNEL,
        PS_US_DOWN, PS_US_PARSE, PS_US_DEFLATE, PS_US_WRITE, PS_US_TOTAL, PS_US_INFLATE, PS_COUNT };
 enum { QS_GIVEN = 0, QS_KEPT, QS_KEYS, QS_LDS, QS_SET, QS_BLOCKS, QS_US_PACK, QS_US_DEVICE, QS_US_KERNEL, QS_US_TOTAL, QS_COUNT };   // dada2hip_sample_set_prior_seqs

@@ -629,6 +629,44 @@ int dada2hip_filter_fastq_paired(dada2hip_filter *ctx, const char *in_f, const c
                                  int64_t chunk_reads, int64_t *reads_in, int64_t *reads_out, int64_t *stats, char *errbuf,
                                  size_t errlen);
 
+/* ---- filterAndTrim's orient.fwd, matchIDs, id.sep and id.field (R/filter.R:648-658, :940-1007) --------------------------------------
+ * The entries above stay as they are; these take the four arguments they do not have.
+ * orient_fwd: 1..256 upper-case A/C/G/T (empty: DADA2HIP_ERR_INPUT; another letter: DADA2HIP_ERR_INPUT "Non-ACGT characters
+ * detected in orient.fwd"; longer: DADA2HIP_ERR_UNSUPPORTED).  A read shorter than it fails the call (narrow() in the reference):
+ * DADA2HIP_ERR_INPUT naming the read.
+ * dada2hip_filter_reads_oriented, orient_mode 0 (single-end): orient[r] is 0 when read r starts with orient_fwd, 1 when only its
+ * reverse complement does, 2 when neither does (3 for the read that failed the call).  A read with 1 goes through every stage AS
+ * its reverse complement - the truncQ cut, the in-order EE sum, the screen's greedy walk and the k-mers are those of the flipped
+ * read - and its window[2 r] counts from the read's END; hits[2 r] is the flipped read's count against the reference.  A read
+ * with 2 has code 12, an empty window and no counts.  Results are in input order (the order of a chunk's output, every 0 and
+ * then every 1, is the file level's).  orient_mode 1 (the paired form): the forward test alone, orient[r] 0 or 2, code[r] 0 or
+ * 12, nothing else is judged or written and `qual` and `params` are not looked at.
+ * dada2hip_filter_fastq_oriented: dada2hip_filter_fastq with orient_fwd; per chunk the reads as given in input order, then the
+ * flipped ones in input order (letters complemented as Biostrings does, qualities reversed, ids unchanged): the output depends on
+ * chunk_reads, as the reference's does on n.
+ * dada2hip_filter_fastq_paired_ex: orient_fwd may be NULL.  With it, a pair whose forward read starts with it stays; one whose
+ * reverse read does (and whose forward read does not) is SWAPPED - each read is judged by, and written to, the other direction -
+ * and the swapped pairs follow the others of their chunk; the rest is dropped.  match_ids != 0: per chunk, with the unmatched
+ * tails of the chunks before in front, the forward records whose id occurs among the reverse ids are kept, and the reverse
+ * records likewise; everything behind a side's last match is carried over.  The id is the header line without '@', split at
+ * id_sep (NULL or "\\s": one of space \t \n \v \f \r; else exactly one literal character) by strsplit's rules, field id_field
+ * (1-based; 0: detected from the first forward id - the one field with 6 colons, else the one with 4, whose forward ids then lose
+ * their '#...' tail and whose reverse ids, as in the reference, do not).  Kept lists of unequal length (duplicate ids) are
+ * DADA2HIP_ERR_INPUT.  Without match_ids unequal chunks are the "Mismatched ..." error of dada2hip_filter_fastq_paired.
+ * stats: the words above and [26] reads (pairs) dropped by orientation, [27] reads flipped (pairs swapped), [28] forward records
+ * without a partner by id, [29] device microseconds of the orientation kernel, [30] host microseconds of the id join. */
+int dada2hip_filter_reads_oriented(dada2hip_filter *ctx, int64_t n, const char *seq, const char *qual, const int64_t *offsets,
+                                   const dada2hip_filter_params *params, const char *orient_fwd, int32_t orient_mode, int32_t *code,
+                                   int32_t *window, double *ee, int32_t *hits, int32_t *kmer_counts, double *complexity, int8_t *orient,
+                                   int64_t *stats, char *errbuf, size_t errlen);
+int dada2hip_filter_fastq_oriented(dada2hip_filter *ctx, const char *in, const char *out, const dada2hip_filter_params *params,
+                                   const char *orient_fwd, int32_t compress, int64_t chunk_reads, int64_t *reads_in, int64_t *reads_out,
+                                   int64_t *stats, char *errbuf, size_t errlen);
+int dada2hip_filter_fastq_paired_ex(dada2hip_filter *ctx, const char *in_f, const char *in_r, const char *out_f, const char *out_r,
+                                    const dada2hip_filter_params *params_f, const dada2hip_filter_params *params_r, const char *orient_fwd,
+                                    int32_t match_ids, const char *id_sep, int32_t id_field, int32_t compress, int64_t chunk_reads,
+                                    int64_t *reads_in, int64_t *reads_out, int64_t *stats, char *errbuf, size_t errlen);
+
 /* ---- removePrimers: primer search on both strands, orientation and trimming (R/filter.R:81-233) ----------------------------------
  * A match of a primer of L letters in a read of n letters is a start st (0-based here, reported 1-based) at which at most
  * max_mismatch of the positions st .. st + L - 1 mismatch; st runs over -max_mismatch .. n - L + max_mismatch and a position outside

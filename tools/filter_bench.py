@@ -5,12 +5,17 @@ truncLen 240, maxEE 2 and the phiX screen.
 
     python tools/filter_bench.py device       # on the GPU
     python tools/filter_bench.py reference    # where the reference's sources are (DADA2_REFERENCE)
+    python tools/filter_bench.py oriented     # on the GPU: orient.fwd and matchIDs (dada2_amd.filtering)
 
 `device` prints one JSON line: reads/s for plain and gzip input and plain and gzip output (best of --repeats), each with the
 library's own clocks (parse, upload, the three kernels, download, deflate, write), and dada2hip_filter_reads on the same reads
 in memory.  `reference` compiles tests/golden/filter_ref_wrap.cpp by the golden generator's recipe and times C_matchRef (both
 strands) + C_matrixEE on a --prefix of the same reads, cut to 240, on ONE thread: the reference's COMPUTE only - not ShortRead's
-parsing, trimming and writing, which this tool cannot run - so the two lines are not a like-for-like ratio."""
+parsing, trimming and writing, which this tool cannot run - so the two lines are not a like-for-like ratio.  `oriented`: every
+read starts with a 20-nt barcode and half of them are stored as their reverse complement; the same reads go through
+dada2hip_filter_reads and dada2hip_filter_reads_oriented in memory and through the plain-to-plain file run both ways, with the
+device time of the orientation kernel and of the scan; then a pair of files that differ in 1 % of their records through
+dada2hip_filter_fastq_paired_ex with match_ids, with the id join's share of the call."""
 import argparse
 import json
 import os
@@ -104,6 +109,82 @@ def device(a):
     print(json.dumps(rec))
 
 
+BARCODE = b"ACGTTGCAAGGCTCATGCTA"
+_COMP = bytes.maketrans(b"ACGT", b"TGCA")
+
+
+def write_fastq_ids(path, ids, seq, qual):
+    with open(path, "wb") as fh:
+        fh.write(b"".join(b"%s\n%s\n+\n%s\n" % (i, s.tobytes(), q.tobytes()) for i, s, q in zip(ids, seq, qual)))
+
+
+def best_of(repeats, f, key=lambda r: r[0]):
+    best = None
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        got = f()
+        r = (time.perf_counter() - t0, got)
+        if best is None or key(r) < key(best):
+            best = r
+    return best
+
+
+def oriented(a):
+    from dada2_amd import api, filtering
+    seq, qual = synth(a.reads, a.len, a.phix, a.seed)
+    seq[:, :len(BARCODE)] = np.frombuffer(BARCODE, dtype=np.uint8)
+    rng = np.random.RandomState(a.seed + 1)
+    rows = rng.choice(a.reads, a.reads // 2, replace=False)                     # stored as the reverse complement
+    seq[rows] = np.frombuffer(seq[rows].tobytes().translate(_COMP), dtype=np.uint8).reshape(len(rows), a.len)[:, ::-1]
+    qual[rows] = qual[rows][:, ::-1]
+    bar = BARCODE.decode()
+    kw = dict(trunc_len=240, max_ee=2)
+    rec = {"tool": "filter_bench", "mode": "oriented", "reads": a.reads, "len": a.len, "phix_share": a.phix, "seed": a.seed, "barcode": bar,
+           "flipped_share": 0.5, "params": {"trunc_len": 240, "max_ee": 2, "rm_phix": True, "n": a.n}}
+    keys = ("parse_us", "upload_us", "orient_device_us", "scan_device_us", "ee_device_us", "download_us", "write_us", "id_join_us", "total_us")
+    with tempfile.TemporaryDirectory() as tmp, api.FilterContext(PHIX_FA) as ctx:
+        seqs, quals = [r.tobytes() for r in seq], [r.tobytes() for r in qual]
+        mem = {}
+        for name, extra in (("plain", {}), ("oriented", {"orient_fwd": bar})):
+            def call():
+                st = {}
+                got = filtering.filter_reads(seqs, quals, ctx, rm_phix=True, stats=st, **kw, **extra)
+                return st, got
+            wall, (st, got) = best_of(a.repeats, call, key=lambda r: r[1][0]["total_us"])
+            mem[name] = dict(python_wall_s=round(wall, 4), library_s=st["total_us"] / 1e6, kept=int((got["code"] == 0).sum()),
+                             flipped=st.get("flipped", 0), **{k: st.get(k, 0) for k in keys})
+        rec["in_memory"] = mem
+        plain, out = os.path.join(tmp, "in.fastq"), os.path.join(tmp, "out.fastq")
+        write_fastq(plain, seq, qual)
+        files = {}
+        for name, extra in (("plain", {}), ("oriented", {"orient_fwd": bar})):
+            def call():
+                st = {}
+                counts = filtering.fastq_filter(plain, out, compress=False, n=a.n, rm_phix=True, ctx=ctx, stats=st, **kw, **extra)
+                return st, counts
+            wall, (st, counts) = best_of(a.repeats, call)
+            files[name] = dict(wall_s=round(wall, 4), reads_per_s=round(a.reads / wall), reads_in=counts[0], reads_out=counts[1],
+                               **{k: st.get(k, 0) for k in keys})
+        rec["plain_to_plain"] = files
+        # ---- a pair of files that differ in 1 % of their records, matched by id ----
+        ids_f = [b"@M01:7:FC:1:%d:%d:%d 1:N:0:ACGT" % (1101 + i // 10**5, i % 10**5, 3 * i) for i in range(a.reads)]
+        ids_r = [i[:-10] + b"2:N:0:ACGT" for i in ids_f]
+        keep_f, keep_r = rng.rand(a.reads) >= 0.005, rng.rand(a.reads) >= 0.005
+        inf, inr, of, orv = (os.path.join(tmp, x) for x in ("F.fastq", "R.fastq", "oF.fastq", "oR.fastq"))
+        write_fastq_ids(inf, [i for i, k in zip(ids_f, keep_f) if k], seq[keep_f], qual[keep_f])
+        write_fastq_ids(inr, [i for i, k in zip(ids_r, keep_r) if k], seq[keep_r], qual[keep_r])
+
+        def pair():
+            st = {}
+            counts = filtering.fastq_paired_filter((inf, inr), (of, orv), compress=False, n=a.n, rm_phix=True, ctx=ctx, stats=st, match_ids=True, **kw)
+            return st, counts
+        wall, (st, counts) = best_of(a.repeats, pair)
+        rec["paired_match_ids"] = dict(wall_s=round(wall, 4), pairs_per_s=round(counts[0] / wall), reads_in=counts[0], reads_out=counts[1],
+                                       records_forward=int(keep_f.sum()), records_reverse=int(keep_r.sum()), dropped_ids=st["dropped_ids"],
+                                       id_join_share_of_call=round(st["id_join_us"] / max(st["total_us"], 1), 4), **{k: st.get(k, 0) for k in keys})
+    print(json.dumps(rec))
+
+
 def reference(a):
     sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
     import make_filter_golden as mg
@@ -129,7 +210,7 @@ def reference(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=("device", "reference"))
+    ap.add_argument("mode", choices=("device", "reference", "oriented"))
     ap.add_argument("--reads", type=int, default=10**6)
     ap.add_argument("--len", type=int, default=250)
     ap.add_argument("--phix", type=float, default=0.01)
@@ -138,7 +219,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=2)
     ap.add_argument("--prefix", type=int, default=20000)
     a = ap.parse_args()
-    (device if a.mode == "device" else reference)(a)
+    {"device": device, "reference": reference, "oriented": oriented}[a.mode](a)
 
 
 if __name__ == "__main__":

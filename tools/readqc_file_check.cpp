@@ -90,6 +90,9 @@ int dada2hip_complexity_reads(int64_t n, const char *seq, const int64_t *offsets
 
 int dada2hip_filter_reads(dada2hip_filter *, int64_t, const char *, const char *, const int64_t *, const dada2hip_filter_params *, int32_t *,
                           int32_t *, double *, int32_t *, int32_t *, double *, int64_t *, char *, size_t) { return DADA2HIP_ERR_DEVICE; }
+int dada2hip_filter_reads_oriented(dada2hip_filter *, int64_t, const char *, const char *, const int64_t *, const dada2hip_filter_params *,
+                                   const char *, int32_t, int32_t *, int32_t *, double *, int32_t *, int32_t *, double *, int8_t *, int64_t *,
+                                   char *, size_t) { return DADA2HIP_ERR_DEVICE; }
 int dada2hip_primers_reads(int64_t, const char *, const int64_t *, const dada2hip_primer_params *, int32_t, int32_t *, int32_t *, int32_t *,
                            int32_t *, int32_t *, int32_t *, int64_t *, char *, size_t) { return DADA2HIP_ERR_DEVICE; }
 int dada2hip_sample_create(int32_t, const char *const *, const int32_t *, const uint8_t *, const double *, int32_t, int32_t,
