@@ -363,13 +363,14 @@ __global__ __launch_bounds__(256) void k_gapless(SampleDev S, int centre, const 
     for (int p = 0; p < L2; p++) {
       if ((p & 15) == 0) { rw = rrow[p >> 4]; cw = p < L1 ? crow[p >> 4] : 0; }
       if ((p & 3) == 0) qw = *(const uint32_t *)(qrow + p);
-      const uint32_t rb = (rw >> ((p & 15) << 1)) & 3u, q = ap.use_quals ? ((qw >> ((p & 3) << 3)) & 255u) : 0u;
+      // (the view feeds the output tables, which go by the quality whatever USE_QUALS says: error.cpp:83-92, :162, :232, :289)
+      const uint32_t rb = (rw >> ((p & 15) << 1)) & 3u, qv = (qw >> ((p & 3) << 3)) & 255u, q = ap.use_quals ? qv : 0u;
       uint32_t t = 5u * rb;
       if (p < L1) {
         const uint32_t cb = (cw >> ((p & 15) << 1)) & 3u;
         t = 4u * cb + rb;
         h += (cb != rb);
-        if (view) view[vr * LV + p] = (uint16_t)(0x8000u | (rb << 8) | q);
+        if (view) view[vr * LV + p] = (uint16_t)(0x8000u | (rb << 8) | qv);
       }
       l = l * s_err[t * ap.ncol + q];
     }
@@ -538,7 +539,7 @@ static __device__ __forceinline__ void nw_traceback_lambda(const NwArgs &a, cons
         t = 4u * cb + rb;
         h += (cb != rb);
         i--;
-        if (a.view && active) a.view[vr * a.LV + i] = (uint16_t)(0x8000u | (rb << 8) | (a.ap.use_quals ? qrow[pj] : 0));
+        if (a.view && active) a.view[vr * a.LV + i] = (uint16_t)(0x8000u | (rb << 8) | qrow[pj]);   // (the tables go by the quality whatever USE_QUALS says)
       } else {
         k--;
       }
@@ -1442,7 +1443,7 @@ __global__ __launch_bounds__(256, 4) void k_nw_ad(NwArgs a, const int32_t *__res
               tc = 4u * cb + rb;
               h += (cb != rb);
               if (a.view && active)
-                a.view[vr * a.LV + pj + dl - 128] = (uint16_t)(0x8000u | (rb << 8) | q);
+                a.view[vr * a.LV + pj + dl - 128] = (uint16_t)(0x8000u | (rb << 8) | qrow[pj]);   // (the tables go by the quality whatever USE_QUALS says)
             }
             rwd[pj] = (tc * (uint32_t)a.ap.ncol + q) << 3;   // &err[t(pj)][q(pj)] - err, in bytes: replaces the base (each position is in ONE run)
           }
@@ -1985,7 +1986,7 @@ __global__ __launch_bounds__(256, 3) void k_nw_adw(NwArgs a, AdwGeom G) {
               tc = 4u * cb + rb;
               h += (cb != rb);
               if (a.view && active)
-                a.view[vr * a.LV + pj + dl] = (uint16_t)(0x8000u | (rb << 8) | (a.ap.use_quals ? qrow[pj] : 0));
+                a.view[vr * a.LV + pj + dl] = (uint16_t)(0x8000u | (rb << 8) | qrow[pj]);   // (the tables go by the quality whatever USE_QUALS says)
             }
             tcode[pj] = (uint8_t)tc;
           }
@@ -2172,7 +2173,7 @@ __global__ __launch_bounds__(256) void k_store(PartState P, SampleDev S, int ci,
       my_skip += (cl == CLS_SKIP);
       if (cl == CLS_SHROUD || cl == CLS_SKIP) { l = 0.0; h = 0xFFFFFFFFu; }   // NULL sub (cluster.cpp:139-143)
       else { l = lam[r]; h = ham[r]; }
-      if (!(l >= 0.0 && l <= 1.0)) atomicOr(P.err_flag, 1);          // "Lambda out-of-range error." (cluster.cpp:184)
+      if (!(l >= 0.0 && l <= 1.0)) atomicOr(P.err_flag, 1);          // "Bad lambda." (pval.cpp:138, :194)
       const double em = P.E_minmax[r];
       keep = l * total_reads > em;                                     // this cluster could attract this raw
       if (keep) {
@@ -2262,7 +2263,7 @@ __global__ __launch_bounds__(256) void k_shuffle(PartState P, SampleDev S, const
       my_skip += (cl == CLS_SKIP);
       if (cl == CLS_SHROUD || cl == CLS_SKIP) { l = 0.0; h = 0xFFFFFFFFu; }   // NULL sub (cluster.cpp:139-143)
       else { l = sa.lam[r]; h = sa.ham[r]; }
-      if (!(l >= 0.0 && l <= 1.0)) atomicOr(P.err_flag, 1);          // "Lambda out-of-range error." (cluster.cpp:184)
+      if (!(l >= 0.0 && l <= 1.0)) atomicOr(P.err_flag, 1);          // "Bad lambda." (pval.cpp:138, :194)
       const double em = P.E_minmax[r];
       keep = l * sa.total_reads > em;                                  // this cluster could attract this raw
       if (keep) {

@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void k2_store0(Eng2 E, const double *__restric
     double l = 0.0;
     uint32_t h = 0xFFFFFFFFu;                                          // NULL sub (cluster.cpp:139-143)
     if (cl == CLS_GAPLESS || cl == CLS_NW) { l = lam[r]; h = ham[r]; }
-    if (!(l >= 0.0 && l <= 1.0)) atomicOr(P.err_flag, 1);              // "Lambda out-of-range error." (cluster.cpp:184)
+    if (!(l >= 0.0 && l <= 1.0)) atomicOr(P.err_flag, 1);              // "Bad lambda." (pval.cpp:138, :194)
     const double em = P.E_minmax[r];
     if (l * E.total_reads > em) {                                      // always: E_minmax starts at -999
       if (l * creads > em) P.E_minmax[r] = l * creads;
@@ -513,7 +513,7 @@ static __device__ D2_SHUF_INLINE void shuffle_body(const Eng2 &E, ShufLds<BS> &L
       if (STORE) {
         if (cl >= CLS_GAPLESS) {
           l = l_raw; h = h_raw;
-          if (!(l >= 0.0 && l <= 1.0)) atomicOr(P.err_flag, 1);        // "Lambda out-of-range error." (cluster.cpp:184)
+          if (!(l >= 0.0 && l <= 1.0)) atomicOr(P.err_flag, 1);        // "Bad lambda." (pval.cpp:138, :194)
           keep = l * E.total_reads > em;                               // this partition could attract this unique
           if (keep) {
             my_keep++;
