@@ -131,6 +131,7 @@ EXPORTS = [
     "dada2hip_qprofile_reads_total", "dada2hip_qprofile_profiled", "dada2hip_qprofile_qual_offset", "dada2hip_qprofile_free",
     "dada2hip_complexity_reads", "dada2hip_complexity_fastq", "dada2hip_complexity_free",
     "dada2hip_bimera_denovo", "dada2hip_bimera_worklist_probe", "dada2hip_bimera_fold_probe",
+    "dada2hip_derep_reads", "dada2hip_filter_derep_fastq", "dada2hip_filter_derep_fastq_paired",
 ]
 
 BIMERA_DENOVO_NSTATS = 16   # DADA2HIP_BIMERA_DENOVO_NSTATS
@@ -201,6 +202,12 @@ QPROFILE_NSCORE = 94   # DADA2HIP_QPROFILE_NSCORE: the quality letters '!' .. '~
 # the int64 words of the stats of dada2hip_qprofile_* / dada2hip_complexity_*, in order
 READQC_STATS = ("reads_in", "reads_profiled", "pieces", "cycles", "upload_bytes", "upload_us", "kernel_device_us", "download_us", "parse_us",
                 "total_us", "open_inflate_us")
+
+
+DEREP_NSTATS = 16   # DADA2HIP_DEREP_NSTATS
+# the int64 words of dada2hip_derep_reads' stats, in order; dada2hip_filter_derep_fastq's are FILTER_NSTATS words of the filter, then these
+DEREP_STATS = ("reads_in", "uniques", "table_capacity", "rebuilds", "collision_rounds", "pieces", "upload_bytes", "download_bytes", "upload_us",
+               "kernel_device_us", "download_us", "finalise_us", "total_us")
 
 
 class CSampleInput(C.Structure):
@@ -395,6 +402,11 @@ def lib():
     L.dada2hip_complexity_fastq.argtypes = [cp, i64, i64, ip, ip, ip, ip, C.POINTER(vp), C.POINTER(i64), vp, cp, C.c_size_t]
     L.dada2hip_complexity_free.argtypes = [vp]
     L.dada2hip_complexity_free.restype = None
+    L.dada2hip_derep_reads.argtypes = [i64, vp, vp, vp, i64, ip, ip, C.POINTER(vp), vp, cp, C.c_size_t]
+    L.dada2hip_filter_derep_fastq.argtypes = [vp, cp, cp, C.POINTER(CFilterParams), ip, i64, i64, ip, C.POINTER(vp), C.POINTER(i64),
+                                              C.POINTER(i64), vp, cp, C.c_size_t]
+    L.dada2hip_filter_derep_fastq_paired.argtypes = [vp, cp, cp, cp, cp, C.POINTER(CFilterParams), C.POINTER(CFilterParams), ip, i64, i64, ip,
+                                                     C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), vp, cp, C.c_size_t]
     L.dada2hip_trim_cache.argtypes = []
     L.dada2hip_trim_cache.restype = None
     _lib = L

@@ -1518,3 +1518,157 @@ int dada2hip_complexity_fastq(const char *path, int64_t chunk_reads, int64_t max
 void dada2hip_complexity_free(double *values) { free(values); }
 
 }  // extern "C"
+
+// ---- the device dereplicator's two ends on the host (derep_dev_host.h has the device between them) ---------------------------------
+// d2_derep_from_rows: the rows of the device into a dada2hip_derep - derep_dev_plain.h's order, means and map over the host pool.
+// dada2hip_filter_derep_fastq, _paired: dada2hip_filter_fastq's chunk pipeline with the kept windows dereplicated on the way -
+// single-end out of the filter's own slots (d2_dd_filter_chunk), a pair's files by a second upload of the kept windows once both
+// verdicts of the chunk are known (d2_dd_feed).  filter_files_body and the entries above are not touched by any of it.
+#include "derep_dev_plain.h"
+
+extern "C" int d2_derep_from_rows(int64_t nuniq, const int64_t *off, const int32_t *len, const int64_t *count, const int64_t *first,
+                                  const uint8_t *bytes, const uint64_t *sums, int64_t nreads, const int32_t *ruid, int64_t chunk_reads,
+                                  int32_t qual_offset, int32_t min_char, dada2hip_derep **out, char *errbuf, size_t errlen) {
+  return filter_files_guarded(errbuf, errlen, [&]() -> int {
+    if (!out) { set_err(errbuf, errlen, "dada2hip: bad arguments"); return DADA2HIP_ERR_INPUT; }
+    *out = nullptr;
+    DdRows R;
+    R.nuniq = nuniq; R.off = off; R.len = len; R.count = count; R.first = first; R.bytes = bytes; R.sums = sums;
+    DdPlan P;
+    const int prc = dd_order(R, chunk_reads > 0 ? chunk_reads : 1000000, P, [](int32_t *f, size_t n, auto less) { pool_sort(f, n, less); });
+    if (prc == DDP_NONE) { set_err(errbuf, errlen, "Only zero-length sequences detected during dereplication."); return DADA2HIP_ERR_INPUT; }
+    if (prc == DDP_OVERFLOW) { set_err(errbuf, errlen, "dada2hip: an abundance or the number of uniques exceeds the integer range."); return DADA2HIP_ERR_INPUT; }
+    const int offset = dd_offset(qual_offset, min_char);
+    const size_t U = (size_t)nuniq, ml = (size_t)P.maxlen;
+    std::unique_ptr<dada2hip_derep> d(new dada2hip_derep());
+    d->nreads = nreads; d->maxlen = P.maxlen;
+    d->abund.resize(U); d->seq_ptrs.resize(U);
+    std::vector<size_t> soff(U + 1, 0);
+    for (size_t k = 0; k < U; k++) soff[k + 1] = soff[k] + (size_t)len[P.order[k]] + 1;
+    d->seq_blob.reset(new char[soff[U]]);
+    d->quals.reset(new double[U * ml]);
+    const double na = na_real();
+    d2::parallel_for(U, 256, [&](size_t k0, size_t k1) {
+      for (size_t k = k0; k < k1; k++) {
+        const int32_t u = P.order[k];
+        d->abund[k] = (int32_t)count[u];
+        dd_quality_row(R, u, offset, P.maxlen, na, &d->quals[k * ml]);
+        char *dst = d->seq_blob.get() + soff[k];
+        memcpy(dst, bytes + off[u], (size_t)len[u]);
+        dst[len[u]] = 0;
+        d->seq_ptrs[k] = dst;
+      }
+    });
+    d->map.resize((size_t)nreads);
+    d2::parallel_for((size_t)nreads, 65536, [&](size_t i0, size_t i1) {
+      for (size_t i = i0; i < i1; i++) d->map[i] = dd_map_entry(ruid[i], P, DADA2HIP_NA_INTEGER);
+    });
+    *out = d.release();
+    return DADA2HIP_OK;
+  });
+}
+
+namespace {
+
+int filter_derep_files_body(dada2hip_filter *ctx, int nfile, const char *const *in, const char *const *out,
+                            const dada2hip_filter_params *const *params, int32_t compress, int64_t chunk_reads, int64_t derep_chunk_reads,
+                            int32_t derep_qual_offset, dada2hip_derep **const *derep, int64_t *reads_in, int64_t *reads_out, int64_t *stats,
+                            char *errbuf, size_t errlen) {
+  FqCall call(reads_in, reads_out);
+  for (int k = 0; k < nfile; k++) {
+    if (!derep[k]) { set_err(errbuf, errlen, "dada2hip: bad arguments"); return DADA2HIP_ERR_INPUT; }
+    *derep[k] = nullptr;
+  }
+  const bool write = out[0] != nullptr;
+  for (int k = 0; k < nfile; k++)
+    if (!in[k] || !params[k] || (out[k] != nullptr) != write) { set_err(errbuf, errlen, "File paths must be provided in character format."); return DADA2HIP_ERR_INPUT; }
+  if (!ctx) { set_err(errbuf, errlen, "dada2hip: no filter context."); return DADA2HIP_ERR_INPUT; }
+  for (int a = 0; a < nfile; a++) {                             // :627, :887
+    for (int b = 0; b < nfile && write; b++)
+      if (strcmp(in[a], out[b]) == 0) {
+        set_err(errbuf, errlen, nfile == 1 ? "The output and input files must be different." : "The output and input file names must be different.");
+        return DADA2HIP_ERR_INPUT;
+      }
+    for (int b = 0; b < a; b++)
+      if ((write && strcmp(out[a], out[b]) == 0) || strcmp(in[a], in[b]) == 0) { set_err(errbuf, errlen, "The output and input file names must be different."); return DADA2HIP_ERR_INPUT; }
+  }
+  struct DdHold { void *p = nullptr; ~DdHold() { if (p) d2_dd_free(p); } } dd[2];
+  // (the dereplicators live on the filter context's device: the first chunk's call says which - d2_dd_filter_chunk checks it)
+  dada2hip_filter_params P[2];
+  for (int k = 0; k < nfile; k++) P[k] = *params[k];
+  int64_t tot[DADA2HIP_FILTER_DEREP_NSTATS] = {0}, st[DADA2HIP_FILTER_NSTATS];
+  std::vector<int32_t> code[2];
+  int32_t device = -1;
+  const int rc = fq_run_chunks(nfile, in, write ? out : nullptr, compress, chunk_reads, tot, FqClockWords{FS_US_PARSE, FS_US_DEFLATE, FS_US_WRITE, FS_US_INFLATE}, call,
+                               [&](FqChunk *ch, bool first, std::vector<uint8_t> &keep, std::vector<int32_t> *win, std::vector<uint8_t> &) -> int {
+    const int64_t n = ch[0].n;
+    if (device < 0) {
+      device = d2_filter_device(ctx);
+      for (int k = 0; k < nfile; k++) {
+        const int r = d2_dd_open(device, derep_chunk_reads, derep_qual_offset, &dd[k].p, errbuf, errlen);
+        if (r != DADA2HIP_OK) return r;
+      }
+    }
+    for (int k = 0; k < nfile; k++) {
+      if (first && P[k].qual_offset == 0) P[k].qual_offset = fq_auto_offset(ch[k]);
+      code[k].resize((size_t)n); win[k].resize(2 * (size_t)n);
+      const int r = nfile == 1 ? d2_dd_filter_chunk(ctx, dd[0].p, n, ch[k].seq.data(), ch[k].qual.data(), ch[k].off.data(), &P[k], code[k].data(),
+                                                    win[k].data(), st, errbuf, errlen)
+                               : dada2hip_filter_reads(ctx, n, ch[k].seq.data(), ch[k].qual.data(), ch[k].off.data(), &P[k], code[k].data(), win[k].data(),
+                                                       nullptr, nullptr, nullptr, nullptr, st, errbuf, errlen);
+      if (r != DADA2HIP_OK) return r;
+      const int w0 = k == 0 ? 0 : FS_CLOCK_FIRST, w1 = k == 0 ? FS_COUNT - 1 : FS_CLOCK_LAST;   // (as filter_files_body)
+      for (int i = w0; i <= w1; i++)
+        if (i >= FS_TAKEN_FIRST && i <= FS_TAKEN_LAST) tot[i] = st[i]; else if (i != FS_US_TOTAL) tot[i] += st[i];
+      for (int64_t i = 0; i < n; i++) if (code[k][i] != 0) keep[i] = 0;
+    }
+    for (int k = 0; k < nfile && nfile == 2; k++) {             // a pair: both objects or neither
+      const int r = d2_dd_feed(dd[k].p, n, ch[k].seq.data(), ch[k].qual.data(), ch[k].off.data(), win[k].data(), keep.data(), errbuf, errlen);
+      if (r != DADA2HIP_OK) return r;
+    }
+    return DADA2HIP_OK;
+  }, errbuf, errlen);
+  if (rc != DADA2HIP_OK) return rc;
+  int64_t *dst = tot + DADA2HIP_FILTER_NSTATS;
+  for (int k = 0; k < nfile && dd[k].p; k++) {
+    int64_t ds[DADA2HIP_DEREP_NSTATS] = {0};
+    const int r = d2_dd_finish(dd[k].p, 1, derep[k], ds, errbuf, errlen);
+    if (r != DADA2HIP_OK) {
+      for (int j = 0; j < nfile; j++) { dada2hip_derep_free(*derep[j]); *derep[j] = nullptr; if (write) (void)remove(out[j]); }
+      return r;
+    }
+    for (int i = 0; i < DD_COUNT; i++)                          // the forward object's words; of the reverse one the bytes and the clocks add
+      if (k == 0) dst[i] = ds[i]; else if (i >= DD_BYTES_UP) dst[i] += ds[i];
+  }
+  return call.finish(tot, sizeof tot, FS_US_TOTAL, stats);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dada2hip_filter_derep_fastq(dada2hip_filter *ctx, const char *in, const char *out, const dada2hip_filter_params *params, int32_t compress,
+                                int64_t chunk_reads, int64_t derep_chunk_reads, int32_t derep_qual_offset, dada2hip_derep **derep,
+                                int64_t *reads_in, int64_t *reads_out, int64_t *stats, char *errbuf, size_t errlen) {
+  dada2hip_derep **const dp[1] = {derep};
+  return filter_files_guarded(errbuf, errlen, [&] {
+    return filter_derep_files_body(ctx, 1, &in, &out, &params, compress, chunk_reads, derep_chunk_reads, derep_qual_offset, dp, reads_in, reads_out,
+                                   stats, errbuf, errlen);
+  });
+}
+
+int dada2hip_filter_derep_fastq_paired(dada2hip_filter *ctx, const char *in_f, const char *in_r, const char *out_f, const char *out_r,
+                                       const dada2hip_filter_params *params_f, const dada2hip_filter_params *params_r, int32_t compress,
+                                       int64_t chunk_reads, int64_t derep_chunk_reads, int32_t derep_qual_offset, dada2hip_derep **derep_f,
+                                       dada2hip_derep **derep_r, int64_t *reads_in, int64_t *reads_out, int64_t *stats, char *errbuf,
+                                       size_t errlen) {
+  const char *in[2] = {in_f, in_r}, *out[2] = {out_f, out_r};
+  const dada2hip_filter_params *params[2] = {params_f, params_r};
+  dada2hip_derep **const dp[2] = {derep_f, derep_r};
+  return filter_files_guarded(errbuf, errlen, [&] {
+    return filter_derep_files_body(ctx, 2, in, out, params, compress, chunk_reads, derep_chunk_reads, derep_qual_offset, dp, reads_in, reads_out,
+                                   stats, errbuf, errlen);
+  });
+}
+
+}  // extern "C"

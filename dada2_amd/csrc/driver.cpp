@@ -17,6 +17,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <exception>
+#include <functional>
 #include <mutex>
 #include <cmath>
 #include <cstdarg>
@@ -3573,6 +3574,7 @@ extern "C++" {
 #include "read_pieces.h"
 #include "readqc_plain.h"
 #include "bimera_plain.h"
+#include "derep_dev_plain.h"
 }
 
 // ---- the sequence-table stage: collapseNoMismatch, nweval (R/multiSample.R:104-160, R/misc.R:216-225) ----
@@ -3592,6 +3594,9 @@ extern "C++" {
 
 // ---- read diagnostics: plotQualityProfile's per-cycle table, seqComplexity with a window (R/plot-methods.R:163-243, R/filter.R:1248-1275) ----
 #include "readqc_host.h"
+
+// ---- derepFastq on the device: reads in memory, or the reads the filter keeps, to a derep object (R/sequenceIO.R:45-183) ----
+#include "derep_dev_host.h"
 
 // ---- priors by sequence on a resident sample: names(uniques) %in% c(priors, pseudo_priors) (R/dada.R:335) ----
 #include "priors_host.h"

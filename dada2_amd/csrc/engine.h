@@ -750,6 +750,35 @@ void launch_bimera_worklist(const int32_t *d_live, int nq, int r0, int wr, int p
 void launch_bimera_fold(const BimeraFold &F, hipStream_t st);
 void launch_calc_pA(int n, const int32_t *d_reads, const double *d_E, const uint8_t *d_prior, double *d_out,
                     hipStream_t st);
+// the device dereplicator (derep_dev.inc.hip).  The state that outlives a piece: an open-addressing table of unique numbers (DD_EMPTY:
+// free; <= -2: claimed in the running round by read -(v + 2) of the piece), per unique its hash, its place in the arena, its
+// length, its count, the smallest index of a read that had it, and in `sums`, beside the arena's bytes, the 64-bit sums of its
+// reads' raw quality characters.  A piece is m reads: read j is seq / qual[start .. start + len) and the idx-th read of the call.
+constexpr int DD_EMPTY = -1;
+constexpr int DD_PENDING = -2, DD_SKIP = -1;   // a read's unique: not settled yet / a zero-length read
+struct DdRead { long long start, idx; int32_t len, pad; };
+struct DdCounters { unsigned long long arena_used; int32_t nuniq, pending, err, minq; };
+struct DdState {
+  int32_t *tab;
+  int cap;                                   // a power of two
+  unsigned long long hmask;                  // DADA2HIP_DEREP_HASH_BITS
+  unsigned long long *u_hash, *u_count, *u_first, *sums;
+  long long *u_off;
+  int32_t *u_len;
+  uint8_t *arena;
+  DdCounters *ctr;
+};
+struct DdPiece {
+  int m;
+  const DdRead *rec;
+  const uint8_t *seq, *qual;
+  unsigned long long *r_hash;
+  int32_t *r_slot, *r_uid, *r_ref;
+  long long auto_reads;                      // reads with idx below it count for the smallest quality character (0: not asked)
+};
+void launch_dd_hash(const DdState &T, const DdPiece &P, hipStream_t st);
+void launch_dd_round(const DdState &T, const DdPiece &P, hipStream_t st);   // claim, verify, publish, settle
+void launch_dd_rebuild(const DdState &T, int nuniq, hipStream_t st);
 
 // final tables from the per-unique aligned views (error.cpp:131-172, :225-258)
 void launch_final_tables(const SampleDev &S, const uint16_t *d_view, int LV, const int32_t *d_work, int nslots,

@@ -28,6 +28,9 @@ struct dada2hip_filter {
 namespace {
 
 using FtSlot = PieceSlot<FilterOut, 4>;
+// what a caller of filter_reads_body may hang behind a piece's scatter: the piece's verdicts stand in the caller's arrays, its
+// stream is idle and its reads still lie in the slot (derep_dev_host.h dereplicates the kept windows out of it)
+using FilterPieceHook = std::function<void(FtSlot &)>;
 
 // the keys of the `len` circular windows of s (filter.inc.hip's form: the two bit planes of the window side by side)
 void ft_strand_keys(const std::string &s, int W, std::vector<unsigned long long> &keys) {
@@ -119,7 +122,7 @@ FilterBarcode filter_barcode(const char *orient_fwd) {
 void filter_reads_body(dada2hip_filter *m, int64_t n, const char *seq, const char *qual, const int64_t *offsets,
                        const dada2hip_filter_params *P, int32_t *code, int32_t *window, double *ee, int32_t *hits, int32_t *kmer_counts,
                        double *complexity, int64_t *stats, const char *orient_fwd = nullptr, int32_t orient_mode = 0,
-                       int8_t *orient = nullptr) {
+                       int8_t *orient = nullptr, const FilterPieceHook *after_piece = nullptr) {
   auto t_call = clk::now();
   int64_t st[DADA2HIP_FILTER_NSTATS] = {0};
   if (!m) throw InputError{"dada2hip: no filter context."};
@@ -254,6 +257,7 @@ void filter_reads_body(dada2hip_filter *m, int64_t n, const char *seq, const cha
     st[FS_KEPT] += dropped[0];
     for (int s = 1; s < 12; s++) st[FS_STAGE1 + s - 1] += dropped[s];
     st[FO_DROPPED_ORIENT] += dropped[FT_CODE_ORIENT];
+    if (after_piece) (*after_piece)(S);
   };
   run_pieces(m->slot, n, seq, only ? nullptr : qual, offsets, knobs().filter_piece, knobs().filter_piece_bytes, want_km ? (size_t)nb : 0, st, FS_BYTES,
              FS_US_UP, FS_US_DOWN, launch, scatter);

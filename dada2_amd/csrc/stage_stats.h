@@ -31,6 +31,10 @@ enum { RQ_IN = 0, RQ_PROFILED, RQ_PIECES, RQ_CYCLES, RQ_BYTES, RQ_US_UP, RQ_US_K
        RQ_COUNT };
 static_assert(RQ_COUNT <= DADA2HIP_READQC_NSTATS && RQ_IN == FS_IN && RQ_PROFILED == FS_KEPT, "stats words; reads in and profiled where a file's reads in and kept are");
 enum { RQ_CALL_FIRST = RQ_PIECES, RQ_CALL_LAST = RQ_US_DOWN };   // the words of a chunk's call that a file adds up (RQ_CYCLES: the largest)
+// the device dereplicator (dada2hip_derep_reads; behind the filter's words in dada2hip_filter_derep_fastq's stats)
+enum { DD_IN = 0, DD_UNIQUES, DD_CAPACITY, DD_REBUILDS, DD_ROUNDS, DD_PIECES, DD_BYTES_UP, DD_BYTES_DOWN, DD_US_UP, DD_US_KERNEL, DD_US_DOWN,
+       DD_US_FINAL, DD_US_TOTAL, DD_COUNT };
+static_assert(DD_COUNT <= DADA2HIP_DEREP_NSTATS, "stats words");
 // How a file adds its chunks' calls up.  Filter: the words of the context are taken, the call's total is the file's own, every other
 // word adds; of a pair's second file only the bytes and the call's clocks add.  Primers: every word of the call adds.
 enum { FS_TAKEN_FIRST = FS_KEYS, FS_TAKEN_LAST = FS_LDS, FS_CLOCK_FIRST = FS_BYTES, FS_CLOCK_LAST = FS_US_DOWN, PS_CALL_LAST = PS_US_DOWN };

@@ -70,6 +70,10 @@
  *   DADA2HIP_PRIMERS_TILE=<n>          ... chunks of 64 match starts per tile of a read (at least 1; default and at most 64)
  *   DADA2HIP_READQC_PIECE=<n>          dada2hip_qprofile_reads, dada2hip_complexity_reads: reads per piece of a call (at least 1; default and at most 65 536)
  *   DADA2HIP_READQC_PIECE_BYTES=<n>    ... bases per piece (at least 1; default and at most 32 MiB; a longer read is a piece of its own)
+ *   DADA2HIP_DEREP_PIECE=<n>           dada2hip_derep_reads: reads per piece of a call (at least 1; default and at most 65 536)
+ *   DADA2HIP_DEREP_PIECE_BYTES=<n>     ... bases per piece (at least 1; default and at most 32 MiB; a longer read is a piece of its own)
+ *   DADA2HIP_DEREP_TABLE=<n>           the device dereplicator: slots of its table at the start (a power of two from 8 on; default 131 072)
+ *   DADA2HIP_DEREP_HASH_BITS=<k>       ... its hash masked to k bits (0..64; default 64; 0: every read collides with every other)
  *   DADA2HIP_PRIORS_LDS_KEYS=<n>       dada2hip_sample_set_prior_seqs: up to n distinct prefix keys are searched in LDS, more in global
  *                                      memory (default 4 096, at most 6 144; 0 = always global memory)
  *   DADA2HIP_BIMERA_SLOTS=<n>          dada2hip_bimera_denovo: work slots per launch (at least one chunk of the aligner; default and at most
@@ -94,6 +98,7 @@ extern "C" {
 #define DADA2HIP_ERR_RUNTIME   3   /* runtime error of the algorithm ("Bad lambda." ...) */
 #define DADA2HIP_ERR_UNSUPPORTED 4 /* input outside what the device path represents (N / IUPAC codes in nwalign, band 0 in nwvec) */
 #define DADA2HIP_ERR_ABORTED   5   /* should_abort() returned non-zero (Rcpp::checkUserInterrupt analogue) */
+#define DADA2HIP_ERR_INTERNAL  6   /* a bound the library sets for itself was reached (the device dereplicator's rounds, its table) */
 
 #define DADA2HIP_NA_INTEGER (-2147483647 - 1)   /* R's NA_integer_ */
 
@@ -407,6 +412,28 @@ void dada2hip_derep_free(dada2hip_derep *d);
 int dada2hip_sample_from_derep(const dada2hip_derep *d, const uint8_t *priors, int32_t device, dada2hip_sample **out,
                                char *errbuf, size_t errlen);
 
+/* ---- dereplication on the device: reads in memory, or the reads filterAndTrim keeps, to a derep object ------------------
+ * dada2hip_derep_reads: n reads in the layout of dada2hip_filter_reads (read r is seq / qual[offsets[r] .. offsets[r + 1]))
+ * to an ordinary dada2hip_derep - every accessor above, dada2hip_sample_from_derep and dada2hip_derep_combine take it - that
+ * equals in every field what dada2hip_derep_fastq returns for a file of these reads: chunks of chunk_reads (<= 0: 1e6), new
+ * uniques of a chunk in C-locale lexical order behind those of earlier chunks, the stable order by decreasing abundance, means
+ * as integer sums divided by the count, NA past a unique's length, map 0-based with NA for zero-length reads; sequences are
+ * compared as bytes.  qual_offset 33, 64 or 0 = Auto, judged on the FIRST chunk only (a character below ';' anywhere in it:
+ * +33, else +64): the raw quality characters are summed in 64-bit words and count x offset is taken off at the end.  n above
+ * 2^31 - 1 and a read above 2^31 - 129 bytes are DADA2HIP_ERR_INPUT; only zero-length reads (or none): DADA2HIP_ERR_INPUT
+ * "Only zero-length sequences detected during dereplication.".  The reads go up in pieces (DADA2HIP_DEREP_PIECE, _PIECE_BYTES);
+ * the table of uniques, their bytes and their sums stay on the device until the call's end, when one row per unique and one
+ * word per read come back; the order, the division and the map's renumbering are the host's.  A round bound or a full table
+ * reached is DADA2HIP_ERR_INTERNAL, never another round.
+ * stats (optional, DADA2HIP_DEREP_NSTATS int64 words): [0] reads in, [1] uniques, [2] the table's capacity at the end, [3] its
+ * rebuilds, [4] collision rounds (rounds of a piece beyond its first: a read that met other bytes under its own hash moved one
+ * slot on), [5] pieces, [6] bytes copied to the device, [7] bytes copied back, [8] host microseconds of the upload, [9] device
+ * microseconds of the derep kernels, [10] host microseconds of the download at the end, [11] of the finalisation, [12] of the
+ * whole call. */
+#define DADA2HIP_DEREP_NSTATS 16
+int dada2hip_derep_reads(int64_t n, const char *seq, const char *qual, const int64_t *offsets, int64_t chunk_reads,
+                         int32_t qual_offset, int32_t device, dada2hip_derep **out, int64_t *stats, char *errbuf, size_t errlen);
+
 /* ---- pooling: the samples' derep objects into one (combineDereps2, R/multiSample.R:165-203; dada(pool = TRUE), R/dada.R:189-192) ----
  * A view is one sample as the accessors above expose it, or as the caller holds it.  dada2hip_derep_combine returns an ordinary
  * dada2hip_derep - every accessor above and dada2hip_sample_from_derep take it - that equals combineDereps2 field for field:
@@ -628,6 +655,31 @@ int dada2hip_filter_fastq_paired(dada2hip_filter *ctx, const char *in_f, const c
                                  const dada2hip_filter_params *params_f, const dada2hip_filter_params *params_r, int32_t compress,
                                  int64_t chunk_reads, int64_t *reads_in, int64_t *reads_out, int64_t *stats, char *errbuf,
                                  size_t errlen);
+
+/* ---- filter and dereplicate in one pass ---------------------------------------------------------------------------------------------
+ * dada2hip_filter_derep_fastq does everything dada2hip_filter_fastq does, and the kept window of every kept read also goes, from
+ * the slot of the filter's pipeline it already lies in and before that slot takes another piece, into the device dereplicator
+ * of dada2hip_derep_reads.  out == NULL: no file is written, deflated or formatted; otherwise the file is byte for byte
+ * dada2hip_filter_fastq's.  *derep is in every field what dada2hip_derep_fastq(out, derep_chunk_reads, derep_qual_offset) returns
+ * for that file: its Auto is judged on the kept windows of the first derep_chunk_reads kept reads (not the filter's own decision,
+ * which is params->qual_offset's), its map has *reads_out entries in file order.  When nothing passes, *derep is NULL, the
+ * return code is DADA2HIP_OK and no file is left.  The pieces are the filter's (DADA2HIP_FILTER_PIECE, _PIECE_BYTES).
+ * dada2hip_filter_derep_fastq_paired is dada2hip_filter_fastq_paired with two derep objects: a pair goes into both or into
+ * neither, so the two maps are equally long and in step (what dada2hip_merge_pairs asks).  A pair's verdict is known only when
+ * both files' pieces have been judged, so the kept windows of a chunk go up once more, through dada2hip_derep_reads' pieces.
+ * stats (optional, DADA2HIP_FILTER_DEREP_NSTATS int64 words): the DADA2HIP_FILTER_NSTATS words of dada2hip_filter_fastq, then
+ * the DADA2HIP_DEREP_NSTATS words of dada2hip_derep_reads (of the forward object, for a pair; the clocks of both added). */
+#define DADA2HIP_FILTER_DEREP_NSTATS (DADA2HIP_FILTER_NSTATS + DADA2HIP_DEREP_NSTATS)
+int dada2hip_filter_derep_fastq(dada2hip_filter *ctx, const char *in, const char *out, const dada2hip_filter_params *params,
+                                int32_t compress, int64_t chunk_reads, int64_t derep_chunk_reads, int32_t derep_qual_offset,
+                                dada2hip_derep **derep, int64_t *reads_in, int64_t *reads_out, int64_t *stats, char *errbuf,
+                                size_t errlen);
+int dada2hip_filter_derep_fastq_paired(dada2hip_filter *ctx, const char *in_f, const char *in_r, const char *out_f,
+                                       const char *out_r, const dada2hip_filter_params *params_f,
+                                       const dada2hip_filter_params *params_r, int32_t compress, int64_t chunk_reads,
+                                       int64_t derep_chunk_reads, int32_t derep_qual_offset, dada2hip_derep **derep_f,
+                                       dada2hip_derep **derep_r, int64_t *reads_in, int64_t *reads_out, int64_t *stats,
+                                       char *errbuf, size_t errlen);
 
 /* ---- filterAndTrim's orient.fwd, matchIDs, id.sep and id.field (R/filter.R:648-658, :940-1007) --------------------------------------
  * The entries above stay as they are; these take the four arguments they do not have.

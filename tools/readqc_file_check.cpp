@@ -97,6 +97,14 @@ int dada2hip_primers_reads(int64_t, const char *, const int64_t *, const dada2hi
                            int32_t *, int32_t *, int32_t *, int64_t *, char *, size_t) { return DADA2HIP_ERR_DEVICE; }
 int dada2hip_sample_create(int32_t, const char *const *, const int32_t *, const uint8_t *, const double *, int32_t, int32_t,
                            dada2hip_sample **, char *, size_t) { return DADA2HIP_ERR_DEVICE; }
+// (the device dereplicator's ends, derep_dev_plain.h: the fused entries of derep.cpp are not run here)
+int d2_dd_open(int32_t, int64_t, int32_t, void **, char *, size_t) { return DADA2HIP_ERR_DEVICE; }
+void d2_dd_free(void *) {}
+int32_t d2_filter_device(const dada2hip_filter *) { return 0; }
+int d2_dd_feed(void *, int64_t, const char *, const char *, const int64_t *, const int32_t *, const uint8_t *, char *, size_t) { return DADA2HIP_ERR_DEVICE; }
+int d2_dd_filter_chunk(dada2hip_filter *, void *, int64_t, const char *, const char *, const int64_t *, const dada2hip_filter_params *, int32_t *,
+                       int32_t *, int64_t *, char *, size_t) { return DADA2HIP_ERR_DEVICE; }
+int d2_dd_finish(void *, int32_t, dada2hip_derep **, int64_t *, char *, size_t) { return DADA2HIP_ERR_DEVICE; }
 
 }  // extern "C"
 
