@@ -132,6 +132,8 @@ EXPORTS = [
     "dada2hip_complexity_reads", "dada2hip_complexity_fastq", "dada2hip_complexity_free",
     "dada2hip_bimera_denovo", "dada2hip_bimera_worklist_probe", "dada2hip_bimera_fold_probe",
     "dada2hip_derep_reads", "dada2hip_filter_derep_fastq", "dada2hip_filter_derep_fastq_paired",
+    "dada2hip_seqtab_merge", "dada2hip_seqtab_nrow", "dada2hip_seqtab_ncol", "dada2hip_seqtab_cells", "dada2hip_seqtab_sequences",
+    "dada2hip_seqtab_samples", "dada2hip_seqtab_free",
 ]
 
 BIMERA_DENOVO_NSTATS = 16   # DADA2HIP_BIMERA_DENOVO_NSTATS
@@ -203,6 +205,12 @@ QPROFILE_NSCORE = 94   # DADA2HIP_QPROFILE_NSCORE: the quality letters '!' .. '~
 READQC_STATS = ("reads_in", "reads_profiled", "pieces", "cycles", "upload_bytes", "upload_us", "kernel_device_us", "download_us", "parse_us",
                 "total_us", "open_inflate_us")
 
+
+SEQTAB_NSTATS = 24   # DADA2HIP_SEQTAB_NSTATS
+# the int64 words of dada2hip_seqtab_merge's stats, in order (the *_us entries are host wall time in microseconds)
+SEQTAB_STATS = ("tables", "input_columns", "distinct_sequences", "flagged_sequences", "output_rows", "output_columns", "table_capacity",
+                "rebuilds", "collision_rounds", "rc_failed_compares", "pieces", "upload_bytes", "download_bytes", "upload_us", "identity_us",
+                "rc_lookup_us", "accumulate_us", "download_us", "total_us")
 
 DEREP_NSTATS = 16   # DADA2HIP_DEREP_NSTATS
 # the int64 words of dada2hip_derep_reads' stats, in order; dada2hip_filter_derep_fastq's are FILTER_NSTATS words of the filter, then these
@@ -403,6 +411,17 @@ def lib():
     L.dada2hip_complexity_free.argtypes = [vp]
     L.dada2hip_complexity_free.restype = None
     L.dada2hip_derep_reads.argtypes = [i64, vp, vp, vp, i64, ip, ip, C.POINTER(vp), vp, cp, C.c_size_t]
+    L.dada2hip_seqtab_merge.argtypes = [ip, vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, ip, C.POINTER(vp), vp, vp, cp, C.c_size_t]
+    for name in ("dada2hip_seqtab_nrow", "dada2hip_seqtab_ncol"):
+        getattr(L, name).argtypes = [vp]
+        getattr(L, name).restype = C.c_int32
+    L.dada2hip_seqtab_cells.argtypes = [vp]
+    L.dada2hip_seqtab_cells.restype = vp
+    for name in ("dada2hip_seqtab_sequences", "dada2hip_seqtab_samples"):
+        getattr(L, name).argtypes = [vp, C.POINTER(vp)]
+        getattr(L, name).restype = vp
+    L.dada2hip_seqtab_free.argtypes = [vp]
+    L.dada2hip_seqtab_free.restype = None
     L.dada2hip_filter_derep_fastq.argtypes = [vp, cp, cp, C.POINTER(CFilterParams), ip, i64, i64, ip, C.POINTER(vp), C.POINTER(i64),
                                               C.POINTER(i64), vp, cp, C.c_size_t]
     L.dada2hip_filter_derep_fastq_paired.argtypes = [vp, cp, cp, cp, cp, C.POINTER(CFilterParams), C.POINTER(CFilterParams), ip, i64, i64, ip,

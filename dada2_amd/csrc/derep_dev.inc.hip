@@ -13,6 +13,8 @@
 //   k_dd_settle   a wave per read settled in this round (r_ref says so; the next round's k_dd_claim clears it): a claimant copies
 //                 its bytes into the arena; the count, the smallest read index and the quality characters are added to the
 //                 unique's by vector atomics.  No lane reads in a launch what another lane of its wave writes in it.
+// A piece with a null `qual` is dereplicated without qualities (seqtab_host.h: the column names of sequence tables): k_dd_hash
+// takes no minimum and k_dd_settle adds no quality characters; the branch is uniform over the launch.
 // Equality is decided on bytes, never on the hash.  No lane waits for another inside a launch: what a launch needs from another
 // lane was written by an EARLIER launch (the hashes, the claims, the numbers), and the one value that changes under a launch, a
 // slot going from free to claimed, is only ever acted on through the compare-and-swap's own answer.  Every loop is bounded by the
@@ -35,7 +37,7 @@ __global__ __launch_bounds__(DD_THREADS) void k_dd_hash(DdState T, DdPiece P) {
   const DdRead R = P.rec[j];
   unsigned long long h = 0;
   int mn = 255;
-  const bool want_min = R.idx < P.auto_reads;
+  const bool want_min = P.qual != nullptr && R.idx < P.auto_reads;   // (a piece without qualities: no minimum)
   for (int p = lane; p < R.len; p += 64) {
     h += dd_mix(((unsigned long long)p << 8) | (unsigned long long)P.seq[R.start + p]);
     if (want_min) mn = min(mn, (int)P.qual[R.start + p]);
@@ -118,7 +120,8 @@ __global__ __launch_bounds__(DD_THREADS) void k_dd_settle(DdState T, DdPiece P) 
   const long long at = T.u_off[u];
   if (ref == j)
     for (int p = lane; p < R.len; p += 64) T.arena[at + p] = P.seq[R.start + p];
-  for (int p = lane; p < R.len; p += 64) atomicAdd(&T.sums[at + p], (unsigned long long)P.qual[R.start + p]);
+  if (P.qual != nullptr && T.sums != nullptr)                    // (wave-uniform; a piece without qualities adds none)
+    for (int p = lane; p < R.len; p += 64) atomicAdd(&T.sums[at + p], (unsigned long long)P.qual[R.start + p]);
   if (lane == 0) {
     atomicAdd(&T.u_count[u], 1ull);
     atomicMin(&T.u_first[u], (unsigned long long)R.idx);

@@ -21,6 +21,7 @@ struct DerepDev {
   int device = 0;
   int64_t chunk_reads = 1000000;
   int32_t qual_offset = 0;
+  bool no_qual = false;                        // seqtab_host.h: strings without qualities - no sums beside the arena, a null `qual`
   Events<2> ev;
   DevBuf<int32_t> tab;
   size_t cap = 0, ucap = 0, acap = 0;
@@ -85,12 +86,13 @@ void dd_reserve(DerepDev &D, int64_t m, int64_t bytes, hipStream_t st) {
     const size_t nc = std::max({need_a, 2 * D.acap, (size_t)1 << 16}), n = (size_t)D.used;
     DevBuf<uint8_t> na;
     DevBuf<unsigned long long> ns;
-    na.alloc(nc); ns.alloc(nc);
+    na.alloc(nc);
+    if (!D.no_qual) ns.alloc(nc);
     if (n) {
       D2_HIP(hipMemcpyAsync(na.p, D.arena.p, n, hipMemcpyDeviceToDevice, st));
-      D2_HIP(hipMemcpyAsync(ns.p, D.sums.p, n * 8, hipMemcpyDeviceToDevice, st));
+      if (!D.no_qual) D2_HIP(hipMemcpyAsync(ns.p, D.sums.p, n * 8, hipMemcpyDeviceToDevice, st));
     }
-    D2_HIP(hipMemsetAsync(ns.p + n, 0, (nc - n) * 8, st));
+    if (!D.no_qual) D2_HIP(hipMemsetAsync(ns.p + n, 0, (nc - n) * 8, st));
     D2_HIP(hipStreamSynchronize(st));
     std::swap(na.p, D.arena.p); std::swap(na.n, D.arena.n); std::swap(ns.p, D.sums.p); std::swap(ns.n, D.sums.n);
     D.acap = nc;
@@ -164,7 +166,7 @@ inline void dd_push(DerepDev &D, int &m, int64_t &bytes, long long start, int32_
 // reads in memory: read r is seq / qual[offsets[r] + window[2 r] .. + window[2 r + 1]) (window null: the whole read), taken if
 // keep[r] (null: every read)
 void dd_feed(DerepDev &D, int64_t n, const char *seq, const char *qual, const int64_t *offsets, const int32_t *window, const uint8_t *keep) {
-  if (n < 0 || (n > 0 && (!seq || !qual || !offsets))) throw InputError{"dada2hip: bad arguments"};
+  if (n < 0 || (n > 0 && (!seq || !offsets || (!qual) != D.no_qual))) throw InputError{"dada2hip: bad arguments"};
   for (int64_t r = 0; r < n; r++) {
     const int64_t l = offsets[r + 1] - offsets[r];
     if (l < 0 || l > (int64_t)INT32_MAX - 128) throw InputError{"dada2hip: bad read offsets."};

@@ -3575,6 +3575,7 @@ extern "C++" {
 #include "readqc_plain.h"
 #include "bimera_plain.h"
 #include "derep_dev_plain.h"
+#include "seqtab_plain.h"
 }
 
 // ---- the sequence-table stage: collapseNoMismatch, nweval (R/multiSample.R:104-160, R/misc.R:216-225) ----
@@ -3597,6 +3598,9 @@ extern "C++" {
 
 // ---- derepFastq on the device: reads in memory, or the reads the filter keeps, to a derep object (R/sequenceIO.R:45-183) ----
 #include "derep_dev_host.h"
+
+// ---- mergeSequenceTables: the column names through the dereplicator, tryRC looked up in its table (R/multiSample.R:290-364) ----
+#include "seqtab_host.h"
 
 // ---- priors by sequence on a resident sample: names(uniques) %in% c(priors, pseudo_priors) (R/dada.R:335) ----
 #include "priors_host.h"

@@ -779,6 +779,22 @@ struct DdPiece {
 void launch_dd_hash(const DdState &T, const DdPiece &P, hipStream_t st);
 void launch_dd_round(const DdState &T, const DdPiece &P, hipStream_t st);   // claim, verify, publish, settle
 void launch_dd_rebuild(const DdState &T, int nuniq, hipStream_t st);
+// A piece with a null `qual` (and a state with null `sums`) is dereplicated without qualities: no smallest character, no sums.
+// mergeSequenceTables on the dereplicator's state (seqtab.inc.hip): the column names of all tables are its "reads".  ST_ERR_*: the
+// error word of StCounters; bad_first: the smallest first appearance (running column number) of a unique with a letter that has no
+// complement; rc_fails: lookups of a reverse complement that met its hash, compared bytes and found them different.
+enum { ST_ERR_WALK = 1, ST_ERR_LETTER = 2, ST_ERR_OVERFLOW = 4 };
+struct StCounters { unsigned long long bad_first, rc_fails; int32_t err, pad; };
+// comp: 256 entries, the complement of a letter or 0 for a letter that has none; partner[u]: the unique that is u's reverse
+// complement (u itself for a palindrome), -1 when the table holds none
+void launch_st_rc(const DdState &T, int nuniq, const uint8_t *d_comp, int32_t *d_partner, StCounters *d_ctr, hipStream_t st);
+// merged[row_map[r] * out_cols + col_map[c]] += cells[r * ncol + c] for a table of nrow x ncol cells, row-major
+void launch_st_accumulate(const int32_t *d_cells, int nrow, int ncol, const int32_t *d_row_map, const int32_t *d_col_map, int32_t *d_merged,
+                          long long out_cols, StCounters *d_ctr, hipStream_t st);
+// per column of the nrow x ncol matrix: the 64-bit sum of its cells and the number of positive ones, added into zeroed arrays
+void launch_st_colkeys(const int32_t *d_merged, long long nrow, long long ncol, unsigned long long *d_sum, int32_t *d_npos, hipStream_t st);
+// out[r * ncol + k] = merged[r * ncol + order[k]]
+void launch_st_gather(const int32_t *d_merged, long long nrow, long long ncol, const int32_t *d_order, int32_t *d_out, hipStream_t st);
 
 // final tables from the per-unique aligned views (error.cpp:131-172, :225-258)
 void launch_final_tables(const SampleDev &S, const uint16_t *d_view, int LV, const int32_t *d_work, int nslots,

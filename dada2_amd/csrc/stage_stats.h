@@ -35,6 +35,10 @@ enum { RQ_CALL_FIRST = RQ_PIECES, RQ_CALL_LAST = RQ_US_DOWN };   // the words of
 enum { DD_IN = 0, DD_UNIQUES, DD_CAPACITY, DD_REBUILDS, DD_ROUNDS, DD_PIECES, DD_BYTES_UP, DD_BYTES_DOWN, DD_US_UP, DD_US_KERNEL, DD_US_DOWN,
        DD_US_FINAL, DD_US_TOTAL, DD_COUNT };
 static_assert(DD_COUNT <= DADA2HIP_DEREP_NSTATS, "stats words");
+// dada2hip_seqtab_merge
+enum { SM_TABLES = 0, SM_COLS_IN, SM_DISTINCT, SM_FLAGGED, SM_ROWS, SM_COLS, SM_CAPACITY, SM_REBUILDS, SM_ROUNDS, SM_RC_FAILS, SM_PIECES,
+       SM_BYTES_UP, SM_BYTES_DOWN, SM_US_UP, SM_US_IDENTITY, SM_US_RC, SM_US_ACCUM, SM_US_DOWN, SM_US_TOTAL, SM_COUNT };
+static_assert(SM_COUNT <= DADA2HIP_SEQTAB_NSTATS, "stats words");
 // How a file adds its chunks' calls up.  Filter: the words of the context are taken, the call's total is the file's own, every other
 // word adds; of a pair's second file only the bytes and the call's clocks add.  Primers: every word of the call adds.
 enum { FS_TAKEN_FIRST = FS_KEYS, FS_TAKEN_LAST = FS_LDS, FS_CLOCK_FIRST = FS_BYTES, FS_CLOCK_LAST = FS_US_DOWN, PS_CALL_LAST = PS_US_DOWN };

@@ -18,6 +18,7 @@
  *   dada2hip_merge_pairs    <- mergePairs()        R/paired.R:92-201 on C_nwalign / C_eval_pair / C_pair_consensus
  *                                                   (src/evaluate.cpp:18-62, :73-114, :124-174)
  *   dada2hip_collapse_nomismatch <- collapseNoMismatch()  R/multiSample.R:104-160 (grepl screen + nwhamming per pair)
+ *   dada2hip_seqtab_merge   <- mergeSequenceTables()   R/multiSample.R:290-364 (validation :206-238)
  *   dada2hip_nweval         <- nweval() / nwhamming()  R/misc.R:216-225
  *   dada2hip_taxonomy_*     <- C_assign_taxonomy2() src/taxonomy.cpp:206-338  (`_dada2_C_assign_taxonomy2`; R/taxonomy.R:135), split into
  *                              the model (:219-270, built once, resident in HBM) and the classification of queries (:113-200)
@@ -518,6 +519,44 @@ int dada2hip_collapse_pairs(int32_t n, const char *const *queries, const char *c
 int dada2hip_nweval(int32_t n, const char *const *s1, const char *const *s2, int32_t match, int32_t mismatch, int32_t gap_p,
                     int32_t homo_gap_p, int32_t band, int32_t endsfree, int32_t vec, int32_t device, int32_t *out,
                     char *errbuf, size_t errlen);
+
+/* ---- mergeSequenceTables (R/multiSample.R:290-364, validation :206-238) ----------------------------------------------------------
+ * dada2hip_seqtab_merge merges ntab >= 2 sequence tables.  Table t is nrow[t] (samples) x ncol[t] (sequences) cells, ROW-major
+ * int32, at cells[t].  The names of all tables lie table after table: column c of the whole call (the running column number) is
+ * col_bytes[col_offsets[c] .. col_offsets[c + 1]), row r is row_bytes[row_offsets[r] .. row_offsets[r + 1]); both offset arrays
+ * have one entry more than names.  repeats_sum 0: a sample name in more than one table is DADA2HIP_ERR_INPUT ("Duplicated sample
+ * names detected in the sequence table row names: a, b"); otherwise such rows are summed at the name's first place.  order_by 0:
+ * the columns stay in order of first appearance; 1: stably by decreasing column sum; 2: by decreasing number of positive cells.
+ * try_rc (used when there is more than one distinct sequence): a sequence whose reverse complement appears EARLIER among the distinct
+ * sequences is renamed to it in every table and leaves the result; a palindrome never is.  Every letter must then be one of
+ * ACGTMRWSYKVHDBN, complemented as Biostrings does; anything else is DADA2HIP_ERR_UNSUPPORTED naming table and column.  Without
+ * try_rc names are compared as bytes and may hold anything.
+ * DADA2HIP_ERR_INPUT: fewer than two tables; an empty table; a negative cell; a blank name; one name twice among a table's columns or
+ * among its rows (the reference only warns); a merged cell above INT32_MAX (NA in the reference).  The sums that order the columns
+ * are 64-bit and never an error.  DADA2HIP_ERR_UNSUPPORTED: two merged matrices and the largest table do not fit in half of the
+ * device's free memory.
+ * The distinct sequences are found by the device dereplicator (DADA2HIP_DEREP_TABLE, _HASH_BITS, _PIECE, _PIECE_BYTES apply), the
+ * reverse complements are looked up in its table, and the cells are added, keyed and reordered on the device.
+ * col_map (optional, one entry per input column, table after table): the 0-based column of the result an input column went to.
+ * stats (optional, DADA2HIP_SEQTAB_NSTATS int64 words): [0] tables, [1] input columns, [2] distinct sequences, [3] sequences
+ * flagged as a reverse complement, [4] rows and [5] columns of the result, [6] the table's capacity, [7] its rebuilds, [8] collision
+ * rounds, [9] reverse-complement lookups that compared bytes and found them different, [10] pieces, [11] bytes copied to the
+ * device, [12] bytes copied back, host microseconds of [13] the uploads of the maps and the cells, [14] the identity of the names
+ * (their upload included) and the plans, [15] the reverse-complement lookup, [16] accumulate + column keys + gather, [17] the
+ * download, [18] the whole call.
+ * The result is owned by the handle until dada2hip_seqtab_free: cells row-major [nrow x ncol]; the names as bytes and offsets. */
+#define DADA2HIP_SEQTAB_NSTATS 24
+typedef struct dada2hip_seqtab dada2hip_seqtab;
+int dada2hip_seqtab_merge(int32_t ntab, const int32_t *nrow, const int32_t *ncol, const int32_t *const *cells, const char *col_bytes,
+                          const int64_t *col_offsets, const char *row_bytes, const int64_t *row_offsets, int32_t repeats_sum,
+                          int32_t order_by, int32_t try_rc, int32_t device, dada2hip_seqtab **out, int32_t *col_map, int64_t *stats,
+                          char *errbuf, size_t errlen);
+int32_t dada2hip_seqtab_nrow(const dada2hip_seqtab *t);
+int32_t dada2hip_seqtab_ncol(const dada2hip_seqtab *t);
+const int32_t *dada2hip_seqtab_cells(const dada2hip_seqtab *t);
+const char *dada2hip_seqtab_sequences(const dada2hip_seqtab *t, const int64_t **offsets);   /* ncol + 1 offsets into the bytes */
+const char *dada2hip_seqtab_samples(const dada2hip_seqtab *t, const int64_t **offsets);     /* nrow + 1 offsets */
+void dada2hip_seqtab_free(dada2hip_seqtab *t);
 
 /* ---- assignTaxonomy: the naive-Bayes 8-mer classifier -----------------------------------------------
  * dada2hip_taxonomy_train builds the model of C_assign_taxonomy2 (src/taxonomy.cpp:219-270) from nref reference sequences,
