@@ -134,6 +134,8 @@ EXPORTS = [
     "dada2hip_derep_reads", "dada2hip_filter_derep_fastq", "dada2hip_filter_derep_fastq_paired",
     "dada2hip_seqtab_merge", "dada2hip_seqtab_nrow", "dada2hip_seqtab_ncol", "dada2hip_seqtab_cells", "dada2hip_seqtab_sequences",
     "dada2hip_seqtab_samples", "dada2hip_seqtab_free",
+    "dada2hip_merge_run", "dada2hip_merge_run_nsamples", "dada2hip_merge_run_nrow", "dada2hip_merge_run_column", "dada2hip_merge_run_sequences",
+    "dada2hip_merge_run_free",
 ]
 
 BIMERA_DENOVO_NSTATS = 16   # DADA2HIP_BIMERA_DENOVO_NSTATS
@@ -211,6 +213,11 @@ SEQTAB_NSTATS = 24   # DADA2HIP_SEQTAB_NSTATS
 SEQTAB_STATS = ("tables", "input_columns", "distinct_sequences", "flagged_sequences", "output_rows", "output_columns", "table_capacity",
                 "rebuilds", "collision_rounds", "rc_failed_compares", "pieces", "upload_bytes", "download_bytes", "upload_us", "identity_us",
                 "rc_lookup_us", "accumulate_us", "download_us", "total_us")
+
+MERGE_NSTATS = 16   # DADA2HIP_MERGE_NSTATS
+# the int64 words of dada2hip_merge_run's stats, in order (the *_us entries are host wall time in microseconds)
+MERGE_STATS = ("samples", "read_pairs_in", "pairs_na", "unique_pairs", "chunks", "accepted", "table_capacity", "collisions", "upload_bytes",
+               "download_bytes", "upload_us", "tally_us", "align_us", "eval_us", "download_us", "total_us")
 
 DEREP_NSTATS = 16   # DADA2HIP_DEREP_NSTATS
 # the int64 words of dada2hip_derep_reads' stats, in order; dada2hip_filter_derep_fastq's are FILTER_NSTATS words of the filter, then these
@@ -422,6 +429,16 @@ def lib():
         getattr(L, name).restype = vp
     L.dada2hip_seqtab_free.argtypes = [vp]
     L.dada2hip_seqtab_free.restype = None
+    L.dada2hip_merge_run.argtypes = [ip] + [vp] * 15 + [ip] * 5 + [C.POINTER(vp), vp, cp, C.c_size_t]
+    L.dada2hip_merge_run_nsamples.argtypes = [vp]
+    L.dada2hip_merge_run_nrow.argtypes = [vp, ip]
+    L.dada2hip_merge_run_nrow.restype = C.c_int64
+    L.dada2hip_merge_run_column.argtypes = [vp, ip, ip]
+    L.dada2hip_merge_run_column.restype = vp
+    L.dada2hip_merge_run_sequences.argtypes = [vp, ip, C.POINTER(vp)]
+    L.dada2hip_merge_run_sequences.restype = vp
+    L.dada2hip_merge_run_free.argtypes = [vp]
+    L.dada2hip_merge_run_free.restype = None
     L.dada2hip_filter_derep_fastq.argtypes = [vp, cp, cp, C.POINTER(CFilterParams), ip, i64, i64, ip, C.POINTER(vp), C.POINTER(i64),
                                               C.POINTER(i64), vp, cp, C.c_size_t]
     L.dada2hip_filter_derep_fastq_paired.argtypes = [vp, cp, cp, cp, cp, C.POINTER(CFilterParams), C.POINTER(CFilterParams), ip, i64, i64, ip,

@@ -3576,6 +3576,7 @@ extern "C++" {
 #include "bimera_plain.h"
 #include "derep_dev_plain.h"
 #include "seqtab_plain.h"
+#include "merge_plain.h"
 }
 
 // ---- the sequence-table stage: collapseNoMismatch, nweval (R/multiSample.R:104-160, R/misc.R:216-225) ----
@@ -3601,6 +3602,9 @@ extern "C++" {
 
 // ---- mergeSequenceTables: the column names through the dereplicator, tryRC looked up in its table (R/multiSample.R:290-364) ----
 #include "seqtab_host.h"
+
+// ---- mergePairs over a run: pairs tallied, every alignment judged and merged on the device (R/paired.R:92-201) ----
+#include "merge_host.h"
 
 // ---- priors by sequence on a resident sample: names(uniques) %in% c(priors, pseudo_priors) (R/dada.R:335) ----
 #include "priors_host.h"

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/dada2hip.h"
+#include "merge_plain.h"   // MpRec, MP_BAD_*: what the tally kernels and the host both name
 
 namespace d2 {
 
@@ -795,6 +796,27 @@ void launch_st_accumulate(const int32_t *d_cells, int nrow, int ncol, const int3
 void launch_st_colkeys(const int32_t *d_merged, long long nrow, long long ncol, unsigned long long *d_sum, int32_t *d_npos, hipStream_t st);
 // out[r * ncol + k] = merged[r * ncol + order[k]]
 void launch_st_gather(const int32_t *d_merged, long long nrow, long long ncol, const int32_t *d_order, int32_t *d_out, hipStream_t st);
+// The run-level mergePairs (merge.inc.hip).  A sample's pair table: open addressing over `cap` slots (a power of two), a slot is
+// its key (f << 32 | r, both 1-based; MP_EMPTY: free), the number of read pairs that name the pair and the first of them.
+// MpCounters: bad_first = (read << 3 | MP_BAD_*) of the first read with an index past a table (~0: none); max_f / max_r the largest
+// entries of the derep maps; nrec the records k_mp_compact has written; collisions the slots walked past; na the read pairs dropped.
+constexpr unsigned long long MP_EMPTY = ~0ull;
+enum { MP_ERR_FULL = 1, MP_ERR_MOVES = 2, MP_ERR_RECORDS = 4 };
+struct MpTable { unsigned long long *key; int32_t *count; uint32_t *first; long long cap; unsigned long long hmask; };   // hmask: DADA2HIP_MERGE_HASH_BITS
+struct MpCounters { unsigned long long bad_first, na, collisions; int32_t max_f, max_r, nrec, err; };
+struct MpSample { const int32_t *derepF, *derepR, *dadaF, *dadaR; int nreads, nuniqF, nuniqR, nclustF, nclustR; };
+// The denoised sequences of the whole run as bytes and offsets, the reverse ones reverse-complemented, with their n0; and the
+// run's unique pairs as indices into them.
+struct MpSeqs { const uint8_t *f_bytes, *r_bytes; const long long *f_off, *r_off; const int32_t *f_n0, *r_n0; };
+struct MpPairs { const int32_t *f, *r; };
+// per pair of a chunk: C_eval_pair's three counts, prefer, accept, the merged length and the leading columns the consensus trims
+struct MpVerdict { int32_t *nmatch, *nmismatch, *nindel, *prefer, *accept, *mlen, *lead; };
+void launch_mp_tally(const MpSample &S, const MpTable &T, MpCounters *d_ctr, hipStream_t st);
+void launch_mp_compact(const MpTable &T, void *d_rec, int max_rec, MpCounters *d_ctr, hipStream_t st);   // d_rec: MpRec (merge_plain.h)
+void launch_mp_eval(const MpSeqs &Q, const MpPairs &P, int npairs, const uint8_t *d_moves, int stride, const int32_t *d_nmoves, int min_overlap,
+                    int max_mismatch, int trim_overhang, const MpVerdict &V, MpCounters *d_ctr, hipStream_t st);
+void launch_mp_consensus(const MpSeqs &Q, const MpPairs &P, int npairs, const uint8_t *d_moves, int stride, const int32_t *d_nmoves,
+                         const MpVerdict &V, const long long *d_off, uint8_t *d_arena, hipStream_t st);
 
 // final tables from the per-unique aligned views (error.cpp:131-172, :225-258)
 void launch_final_tables(const SampleDev &S, const uint16_t *d_view, int LV, const int32_t *d_work, int nslots,

@@ -2913,6 +2913,7 @@ void launch_bimera_lr(const SampleDev &S, const int32_t *d_chunk_centre, const i
 #include "readqc.inc.hip"    // read diagnostics: the per-cycle quality table; the windowed k-mer complexity of a read
 #include "derep_dev.inc.hip" // the device dereplicator: hash, claim, verify, publish, settle; the table's rebuild
 #include "seqtab.inc.hip"    // mergeSequenceTables: the reverse complement's lookup in the dereplicator's table, accumulate, column keys, gather
+#include "merge.inc.hip"     // mergePairs over a run: the pair table of a sample, C_eval_pair and C_pair_consensus on the aligner's move strings
 #include "priors.inc.hip"    // priors by sequence: a lane per resident unique, its prefix key searched among the prior sequences' keys
 #include "bimera_denovo.inc.hip"   // isBimeraDenovo: the work lists of a window of parent ranks, the fold of its records into six maxima per query
 

@@ -39,6 +39,10 @@ static_assert(DD_COUNT <= DADA2HIP_DEREP_NSTATS, "stats words");
 enum { SM_TABLES = 0, SM_COLS_IN, SM_DISTINCT, SM_FLAGGED, SM_ROWS, SM_COLS, SM_CAPACITY, SM_REBUILDS, SM_ROUNDS, SM_RC_FAILS, SM_PIECES,
        SM_BYTES_UP, SM_BYTES_DOWN, SM_US_UP, SM_US_IDENTITY, SM_US_RC, SM_US_ACCUM, SM_US_DOWN, SM_US_TOTAL, SM_COUNT };
 static_assert(SM_COUNT <= DADA2HIP_SEQTAB_NSTATS, "stats words");
+// dada2hip_merge_run
+enum { MR_SAMPLES = 0, MR_PAIRS_IN, MR_NA, MR_UNIQUE, MR_CHUNKS, MR_ACCEPTED, MR_CAPACITY, MR_COLLISIONS, MR_BYTES_UP, MR_BYTES_DOWN, MR_US_UP,
+       MR_US_TALLY, MR_US_ALIGN, MR_US_EVAL, MR_US_DOWN, MR_US_TOTAL, MR_COUNT };
+static_assert(MR_COUNT <= DADA2HIP_MERGE_NSTATS, "stats words");
 // How a file adds its chunks' calls up.  Filter: the words of the context are taken, the call's total is the file's own, every other
 // word adds; of a pair's second file only the bytes and the call's clocks add.  Primers: every word of the call adds.
 enum { FS_TAKEN_FIRST = FS_KEYS, FS_TAKEN_LAST = FS_LDS, FS_CLOCK_FIRST = FS_BYTES, FS_CLOCK_LAST = FS_US_DOWN, PS_CALL_LAST = PS_US_DOWN };

@@ -19,6 +19,7 @@
  *                                                   (src/evaluate.cpp:18-62, :73-114, :124-174)
  *   dada2hip_collapse_nomismatch <- collapseNoMismatch()  R/multiSample.R:104-160 (grepl screen + nwhamming per pair)
  *   dada2hip_seqtab_merge   <- mergeSequenceTables()   R/multiSample.R:290-364 (validation :206-238)
+ *   dada2hip_merge_run      <- mergePairs() over the samples of a run  R/paired.R:92-201 (the pairs tallied, judged and merged on the device)
  *   dada2hip_nweval         <- nweval() / nwhamming()  R/misc.R:216-225
  *   dada2hip_taxonomy_*     <- C_assign_taxonomy2() src/taxonomy.cpp:206-338  (`_dada2_C_assign_taxonomy2`; R/taxonomy.R:135), split into
  *                              the model (:219-270, built once, resident in HBM) and the classification of queries (:113-200)
@@ -75,6 +76,8 @@
  *   DADA2HIP_DEREP_PIECE_BYTES=<n>     ... bases per piece (at least 1; default and at most 32 MiB; a longer read is a piece of its own)
  *   DADA2HIP_DEREP_TABLE=<n>           the device dereplicator: slots of its table at the start (a power of two from 8 on; default 131 072)
  *   DADA2HIP_DEREP_HASH_BITS=<k>       ... its hash masked to k bits (0..64; default 64; 0: every read collides with every other)
+ *   DADA2HIP_MERGE_HASH_BITS=<k>       dada2hip_merge_run: the pair table's hash masked to k bits (0..64; default 64; 0: every pair walks from slot 0)
+ *   DADA2HIP_MERGE_CHUNK=<n>           ... unique pairs per chunk of the aligner (at least 1; default and at most 65 536)
  *   DADA2HIP_PRIORS_LDS_KEYS=<n>       dada2hip_sample_set_prior_seqs: up to n distinct prefix keys are searched in LDS, more in global
  *                                      memory (default 4 096, at most 6 144; 0 = always global memory)
  *   DADA2HIP_BIMERA_SLOTS=<n>          dada2hip_bimera_denovo: work slots per launch (at least one chunk of the aligner; default and at most
@@ -557,6 +560,46 @@ const int32_t *dada2hip_seqtab_cells(const dada2hip_seqtab *t);
 const char *dada2hip_seqtab_sequences(const dada2hip_seqtab *t, const int64_t **offsets);   /* ncol + 1 offsets into the bytes */
 const char *dada2hip_seqtab_samples(const dada2hip_seqtab *t, const int64_t **offsets);     /* nrow + 1 offsets */
 void dada2hip_seqtab_free(dada2hip_seqtab *t);
+
+/* ---- mergePairs over a run (R/paired.R:92-201) -------------------------------------------------------------------------------
+ * dada2hip_merge_run == lapply(seq_along(dadaF), ...) of mergePairs() for nsamples samples in one call; dada2hip_merge_pairs above
+ * is the one-sample entry and is unchanged.  Per sample s: nreads[s] read pairs; derepF_map[s] / derepR_map[s] the derep-class
+ * maps (0-BASED unique of every read; any negative value is NA); dadaF_map[s] / dadaR_map[s] the dada-class maps of nuniqF[s] /
+ * nuniqR[s] uniques (1-BASED denoised sequence; <= 0, NA_INTEGER included, is NA).  The clustering tables of all samples stand
+ * one behind the other: sample s has nclustF[s] forward sequences, sequence i of the run is seqF_bytes[seqF_offsets[i] ..
+ * seqF_offsets[i + 1]) with n0F[i]; the reverse side alike.
+ * On the device: a lane per read pair gathers f = dadaF_map[derepF_map[i]] and r, drops the pair when either step is NA and counts
+ * (f, r) in the sample's own open-addressing table with the first read that had it (unique(pairdf), table(): :125, :175); the
+ * unique pairs of ALL samples are aligned in chunks by the pair-form lane aligner as nwalign(F, rc(R), band = -1) with the scores
+ * of :153-158; C_eval_pair (nmatch, nmismatch, nindel), prefer, accept (:165-166) and C_pair_consensus are computed from the move
+ * strings where the aligner left them.  Six integers per pair and the accepted sequences come back.  With just_concatenate
+ * nothing is aligned (:140-148).  Rows per sample in the reference's order: first appearance, stably by decreasing abundance.
+ * Errors.  DADA2HIP_ERR_INPUT: a map of more than INT32_MAX reads; the reference's "Non-corresponding derep-class and dada-class
+ * objects." where the largest entry of a derep map is not the last unique of the dada-class object (:116-119; an empty map or one
+ * of NAs alone included), with the sample (counted from 1); the same message for an index past either table, with the sample and
+ * the first read (counted from 0) that holds one.  DADA2HIP_ERR_UNSUPPORTED: a denoised sequence that is empty or has a letter
+ * outside A/C/G/T (dada() produces none), unless just_concatenate.
+ * stats (optional, DADA2HIP_MERGE_NSTATS int64 words): [0] samples, [1] read pairs in, [2] of them dropped as NA, [3] unique pairs,
+ * [4] chunks, [5] pairs accepted, [6] the largest table's capacity, [7] slots walked past by inserts, [8] bytes copied to the
+ * device, [9] bytes copied back, host microseconds of [10] the uploads, [11] the tally (tables, records, order), [12] the
+ * alignments (the throw-away sample included), [13] eval + consensus, [14] the downloads, [15] the whole call.
+ * The result is owned by the handle until dada2hip_merge_run_free.  dada2hip_merge_run_column: `which` 0..7 = abundance, forward,
+ * reverse, nmatch, nmismatch, nindel, prefer (NA_INTEGER with just_concatenate), accept - nrow(sample) entries, rejects included.
+ * dada2hip_merge_run_sequences: the bytes of the whole run and, through `offsets`, the nrow(sample) + 1 offsets of the sample's rows
+ * into them ("" for a reject). */
+#define DADA2HIP_MERGE_NSTATS 16
+typedef struct dada2hip_run_mergers dada2hip_run_mergers;
+int dada2hip_merge_run(int32_t nsamples, const int64_t *nreads, const int32_t *const *derepF_map, const int32_t *const *derepR_map,
+                       const int32_t *nuniqF, const int32_t *const *dadaF_map, const int32_t *nuniqR, const int32_t *const *dadaR_map,
+                       const int32_t *nclustF, const char *seqF_bytes, const int64_t *seqF_offsets, const int32_t *n0F, const int32_t *nclustR,
+                       const char *seqR_bytes, const int64_t *seqR_offsets, const int32_t *n0R, int32_t min_overlap, int32_t max_mismatch,
+                       int32_t trim_overhang, int32_t just_concatenate, int32_t device, dada2hip_run_mergers **out, int64_t *stats, char *errbuf,
+                       size_t errlen);
+int32_t dada2hip_merge_run_nsamples(const dada2hip_run_mergers *m);
+int64_t dada2hip_merge_run_nrow(const dada2hip_run_mergers *m, int32_t sample);
+const int32_t *dada2hip_merge_run_column(const dada2hip_run_mergers *m, int32_t sample, int32_t which);
+const char *dada2hip_merge_run_sequences(const dada2hip_run_mergers *m, int32_t sample, const int64_t **offsets);
+void dada2hip_merge_run_free(dada2hip_run_mergers *m);
 
 /* ---- assignTaxonomy: the naive-Bayes 8-mer classifier -----------------------------------------------
  * dada2hip_taxonomy_train builds the model of C_assign_taxonomy2 (src/taxonomy.cpp:219-270) from nref reference sequences,
