@@ -31,6 +31,7 @@
 #include "engine.h"
 #include "hostpar.h"
 #include "knobs.h"
+#include "marshal.h"
 #include "ppois.h"
 
 namespace d2 {
@@ -76,6 +77,7 @@ template <typename T> struct PinBuf {
   PinBuf(const PinBuf &) = delete;
   PinBuf &operator=(const PinBuf &) = delete;
   ~PinBuf() { if (p) AllocCache::get().pin_release(p); }
+  void free() { if (p) AllocCache::get().pin_release(p); p = nullptr; n = 0; }
   void alloc(size_t count) {
     if (count <= n && p) return;
     if (p) { AllocCache::get().pin_release(p); p = nullptr; }
@@ -108,7 +110,16 @@ struct dada2hip_sample {
   uint64_t total_reads = 0;
   int qmax = 0;
   double ms_upload = 0;
-  double ms_upload_part[5] = {0, 0, 0, 0, 0};   // lengths, packing (+ its copies and the k-mer launch), quality conversion, wait side, wait main
+  double ms_upload_part[5] = {0, 0, 0, 0, 0};   // the fused pass's enqueue share (copies, k-mer launches), the fused pass, buffers + checks, wait side, wait main
+  // Pinned sources of the upload's copies (sample_create): quality bytes, and len / reads / prior side by side.  The boundary call
+  // does not wait for the copies between create and run, so they live here until the run's first stream wait (sample_run);
+  // ev_up is recorded on the side stream behind the last quality chunk and the main stream waits for it on the device.
+  PinBuf<uint8_t> up_qual;
+  PinBuf<int32_t> up_meta;
+  hipEvent_t ev_up = nullptr;
+  // the last run's final work list as it lies in d_work / d_chunk_centre (dada2hip_sample_final_worklist: the tests read it back)
+  int64_t fin_nwork = 0, fin_nchunk = 0;
+  int32_t fin_per = 0, fin_on_device = 0;
   // per-run device work buffers (kept across runs: selfConsist passes reuse them)
   DevBuf<uint8_t> d_skip, d_cls, d_correct, d_moves;
   DevBuf<double> d_lambda, d_err;
@@ -285,15 +296,21 @@ int nw_sentinel(const dada2hip_opts &o) {
 // ---- sample creation: validate (Rmain.cpp:52-78), pack, upload, build k-mer records -------------
 // The reference copies its inputs out of the R objects serially (Rmain.cpp:102-120).  At 10^6 uniques x 250 nt the
 // boundary hands over 250 MB of characters and 2 GB of doubles, so the marshalling is spread over the host pool:
-//   pass 1  strlen / abundance / prior per unique                                  (threads)
-//   pass 2  2-bit packing + ACGT validation straight into a pinned buffer          (threads)  -> one async H2D
-//   pass 3  (uint8) round(mean quality) of raw_new (containers.cpp:34) into pinned bytes, ONE job over all rows (threads);
-//           each 16 MB chunk goes out on the side stream when its last piece is done, overlapping the conversion of the
-//           chunks behind it and the k-mer build on the main stream
-// Passes 2 and 3 run hostsimd.cpp's loops (explicit AVX2 where the CPU has it).
-// lite = nwalign / nwvec helper samples: no qualities, no k-mer records, any length >= 1.
+// ONE job over all rows (hostsimd.cpp's marshal_rows, explicit AVX2 where the CPU has it).  The caller states the row geometry
+// (quals_nrow must equal the longest read), so nothing has to be measured before the buffers can be laid out: a piece of 512 rows
+// takes its rows' strlen / abundance / prior, packs them into 2-bit words straight into pinned memory (validating ACGT) and
+// rounds their qualities ((uint8) round(mean quality) of raw_new, containers.cpp:34) into pinned bytes.  A chunk is whole
+// pieces, about 16 MB of quality bytes; the thread that finishes a chunk's last rows queues its copies, in chunk order - the
+// quality bytes on the side stream, the packed rows, len, reads and prior on the main stream - while the chunks behind it are
+// still being converted, and behind them the k-mer build of the chunk's rows.  The input errors are raised behind the job, in
+// the order and with the texts of the reference's checks; the one kernel that runs before them is launched only on rows whose
+// lengths fit the stated geometry, and what it wrote for an input that then fails is never used.
+// defer: the caller (the boundary call) runs the sample next and does not need the upload to be over when this returns - the
+// main stream waits for the side stream's copies on the device, the pinned sources stay with the sample (sample_run).
+// lite = nwalign / nwvec helper samples: no qualities, no k-mer records, any length >= 1, no stated geometry: lengths first
+// (one pass), then the packing (a second one), one copy.
 void sample_create(dada2hip_sample *s, int32_t nraw, const char *const *seqs, const int32_t *abund,
-                   const uint8_t *priors, const double *quals, int32_t quals_nrow, int device, bool lite = false) {
+                   const uint8_t *priors, const double *quals, int32_t quals_nrow, int device, bool lite = false, bool defer = false) {
   auto t0 = clk::now();
   auto t_lap = t0;
   auto lap = [&](int k) { s->ms_upload_part[k] = ms_since(t_lap); t_lap = clk::now(); };   // (DADA2HIP_V2_SUMMARY: the upload's split)
@@ -302,69 +319,91 @@ void sample_create(dada2hip_sample *s, int32_t nraw, const char *const *seqs, co
   s->h_len.resize(nraw);
   s->h_reads.resize(nraw);
   s->h_prior.assign(nraw, 0);
-  std::atomic<int> amax{0}, amin{SEQLEN};
-  std::atomic<uint64_t> atot{0};
-  parallel_for((size_t)nraw, 8192, [&](size_t lo, size_t hi) {
-    int mx = 0, mn = SEQLEN;
-    uint64_t tot = 0;
-    for (size_t i = lo; i < hi; i++) {
-      const int l = (int)strnlen(seqs[i], (size_t)SEQLEN + 1);
-      s->h_len[i] = l;
-      mx = std::max(mx, l); mn = std::min(mn, l);
-      s->h_reads[i] = (uint32_t)abund[i];
-      tot += (uint32_t)abund[i];
-      if (priors) s->h_prior[i] = priors[i] ? 1 : 0;
-    }
-    int cur = amax.load();
-    while (mx > cur && !amax.compare_exchange_weak(cur, mx)) {}
-    cur = amin.load();
-    while (mn < cur && !amin.compare_exchange_weak(cur, mn)) {}
-    atot += tot;
-  });
-  const int maxlen = amax.load(), minlen = amin.load();
-  s->total_reads = atot.load();
-  lap(0);
-  if (maxlen >= SEQLEN) throw InputError{"Input sequences exceed the maximum allowed string length."};
-  if (!lite) {
-    if (minlen <= KMER_SIZE) throw InputError{"Input sequences must all be longer than the kmer-size (5)."};
-    if (!quals)
-      throw InputError{"dada2hip: a quality matrix is required (the reference reads it unconditionally, src/error.cpp:158)."};
-    if (quals_nrow != maxlen) throw InputError{"Sequence must have associated qualities for each nucleotide position."};
-  } else if (minlen < 1) throw InputError{"dada2hip: empty sequence."};
+  int maxlen = 0, minlen = SEQLEN;
+  // lengths / abundances / priors alone: the lite samples' first pass, and what an input that states no usable geometry gets
+  auto measure_rows = [&]() {
+    std::atomic<int> amax{0}, amin{SEQLEN};
+    std::atomic<uint64_t> atot{0};
+    parallel_for((size_t)nraw, 8192, [&](size_t lo, size_t hi) {
+      int mx = 0, mn = SEQLEN;
+      uint64_t tot = 0;
+      for (size_t i = lo; i < hi; i++) {
+        const int l = (int)strnlen(seqs[i], (size_t)SEQLEN + 1);
+        s->h_len[i] = l;
+        mx = std::max(mx, l); mn = std::min(mn, l);
+        s->h_reads[i] = (uint32_t)abund[i];
+        tot += (uint32_t)abund[i];
+        if (priors) s->h_prior[i] = priors[i] ? 1 : 0;
+      }
+      int cur = amax.load();
+      while (mx > cur && !amax.compare_exchange_weak(cur, mx)) {}
+      cur = amin.load();
+      while (mn < cur && !amin.compare_exchange_weak(cur, mn)) {}
+      atot += tot;
+    });
+    maxlen = amax.load(); minlen = amin.load();
+    s->total_reads = atot.load();
+  };
+  // the checks that need the lengths only, in the reference's order (Rmain.cpp:52-78)
+  auto check_lengths = [&]() {
+    if (maxlen >= SEQLEN) throw InputError{"Input sequences exceed the maximum allowed string length."};
+    if (!lite) {
+      if (minlen <= KMER_SIZE) throw InputError{"Input sequences must all be longer than the kmer-size (5)."};
+      if (!quals)
+        throw InputError{"dada2hip: a quality matrix is required (the reference reads it unconditionally, src/error.cpp:158)."};
+      if (quals_nrow != maxlen) throw InputError{"Sequence must have associated qualities for each nucleotide position."};
+    } else if (minlen < 1) throw InputError{"dada2hip: empty sequence."};
+  };
+  // the fused pass lays its buffers out by the stated row length; an input without one fails one of the checks above
+  const bool fused = !lite && quals && quals_nrow >= 1 && quals_nrow < SEQLEN;
+  if (!fused) {
+    measure_rows();
+    lap(0);
+    check_lengths();
+    if (!lite) throw RuntimeErr{DADA2HIP_ERR_RUNTIME, "dada2hip: an input without a usable row length passed its checks"};
+  }
 
-  select_device(device);
+  try {
+    select_device(device);
+  } catch (const DeviceError &) {   // (no device: an input error of the lengths still comes first, as it did when they were measured first)
+    if (fused) { measure_rows(); check_lengths(); }
+    throw;
+  }
   s->device = device;
   D2_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
   D2_HIP(hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking));
   D2_HIP(hipEventCreate(&s->ev0));
   D2_HIP(hipEventCreate(&s->ev1));
   SampleDev &D = s->D;
-  D.N = nraw; D.maxlen = maxlen; D.minlen = minlen;
+  const int rowlen = fused ? (int)quals_nrow : maxlen;          // (= maxlen for every input that passes the checks)
+  D.N = nraw; D.maxlen = rowlen; D.minlen = minlen;
   D.r_lo = 0; D.r_hi = nraw;
-  D.W2 = (((maxlen + 15) / 16) + 3) & ~3;
-  D.LQ = (maxlen + 15) & ~15;
-  D.LK = (std::max(maxlen - KMER_SIZE + 1, 1) + 7) & ~7;
-  D.HMAX = std::max(0, (maxlen - KMER_SIZE + 1) / (RANK_SAT + 1));
+  D.W2 = (((rowlen + 15) / 16) + 3) & ~3;
+  D.LQ = (rowlen + 15) & ~15;
+  D.LK = (std::max(rowlen - KMER_SIZE + 1, 1) + 7) & ~7;
+  D.HMAX = std::max(0, (rowlen - KMER_SIZE + 1) / (RANK_SAT + 1));
 
-  // 2-bit packing on the host pool, straight into pinned memory (validates ACGT: R checks C_isACGT before the call,
-  // R/dada.R:269); the pinned rows stay as the host mirror of the sequences (result strings are decoded from them)
+  // the pinned rows of 2-bit words stay as the host mirror of the sequences (result strings are decoded from them)
   s->h_seq2.alloc((size_t)nraw * D.W2);
-  std::atomic<int> bad{0};
   const int W2 = D.W2;
   uint32_t *packed = s->h_seq2.p;
-  parallel_for((size_t)nraw, 2048, [&](size_t lo, size_t hi) {
-    uint32_t any = 0;                                            // one accumulator per piece, no store per base
-    for (size_t i = lo; i < hi; i++) any |= d2::pack_row_2bit(seqs[i], s->h_len[i], packed + i * W2, W2);
-    if (any) bad.store(1, std::memory_order_relaxed);
-  });
-  if (bad.load()) throw InputError{"Invalid derep$uniques vector. Sequences must be made up only of A/C/G/T."};
+  if (lite) {
+    // 2-bit packing on the host pool, straight into pinned memory (validates ACGT: R checks C_isACGT before the call, R/dada.R:269)
+    std::atomic<int> bad{0};
+    parallel_for((size_t)nraw, 2048, [&](size_t lo, size_t hi) {
+      uint32_t any = 0;                                            // one accumulator per piece, no store per base
+      for (size_t i = lo; i < hi; i++) any |= d2::pack_row_2bit(seqs[i], s->h_len[i], packed + i * W2, W2);
+      if (any) bad.store(1, std::memory_order_relaxed);
+    });
+    if (bad.load()) throw InputError{"Invalid derep$uniques vector. Sequences must be made up only of A/C/G/T."};
+  }
   s->seq2.alloc((size_t)nraw * D.W2);
   s->nwflag.alloc(1);
   D.nw_flag = s->nwflag.p;
   {   // pointer ring of k_nw_ad (kernels.hip): 8 192 wave slots of 8 KB at 250 nt; fewer, never below 1 024, for long reads.
       // Only its geometry here: the 64-256 MB are taken for the duration of a run (ensure_ad_ring) - the throw-away
       // samples of nwvec / merge / bimera never need them, and hundreds of resident samples would each have held one
-    D.ad_wpw = 64 * ((2 * maxlen + 1 + 15) / 16);
+    D.ad_wpw = 64 * ((2 * rowlen + 1 + 15) / 16);
     int waves = 8192;
     while (waves > 1024 && (size_t)waves * D.ad_wpw * 4 > ((size_t)256 << 20)) waves /= 2;
     D.ad_ptr = nullptr;
@@ -375,11 +414,11 @@ void sample_create(dada2hip_sample *s, int32_t nraw, const char *const *seqs, co
   s->qual.alloc((size_t)nraw * D.LQ);
   D.seq2 = s->seq2.p; D.len = s->len.p; D.reads = s->reads.p; D.prior = s->prior.p; D.nheavy = s->nheavy.p;
   D.qual = s->qual.p;
-  D2_HIP(hipMemcpyAsync(D.seq2, packed, (size_t)nraw * D.W2 * 4, hipMemcpyHostToDevice, s->stream));
-  D2_HIP(hipMemcpyAsync(D.len, s->h_len.data(), (size_t)nraw * 4, hipMemcpyHostToDevice, s->stream));
-  D2_HIP(hipMemcpyAsync(D.reads, s->h_reads.data(), (size_t)nraw * 4, hipMemcpyHostToDevice, s->stream));
-  D2_HIP(hipMemcpyAsync(D.prior, s->h_prior.data(), (size_t)nraw, hipMemcpyHostToDevice, s->stream));
   if (lite) {
+    D2_HIP(hipMemcpyAsync(D.seq2, packed, (size_t)nraw * D.W2 * 4, hipMemcpyHostToDevice, s->stream));
+    D2_HIP(hipMemcpyAsync(D.len, s->h_len.data(), (size_t)nraw * 4, hipMemcpyHostToDevice, s->stream));
+    D2_HIP(hipMemcpyAsync(D.reads, s->h_reads.data(), (size_t)nraw * 4, hipMemcpyHostToDevice, s->stream));
+    D2_HIP(hipMemcpyAsync(D.prior, s->h_prior.data(), (size_t)nraw, hipMemcpyHostToDevice, s->stream));
     D2_HIP(hipMemsetAsync(D.qual, 0, (size_t)nraw * D.LQ, s->stream));
     D2_HIP(hipStreamSynchronize(s->stream));
     s->qmax = 0;
@@ -391,22 +430,29 @@ void sample_create(dada2hip_sample *s, int32_t nraw, const char *const *seqs, co
   D.kord = s->kord.p; D.heavy = s->heavy.p;
   // 5-mer presence bitmaps for the batch screen's prefilter: worth their 128 B per unique while a read's k-mers leave most of
   // the 1024 bits clear (250 nt: ~215 set).  Long reads fill them (1 500 nt: ~800 set, the bound never decides) - none there
-  if (maxlen - KMER_SIZE + 1 <= 512 && knobs().screen_bits != 0) {
+  if (rowlen - KMER_SIZE + 1 <= 512 && knobs().screen_bits != 0) {
     s->kbits.alloc((size_t)nraw * 32); s->kmult.alloc(nraw);
     D.kbits = s->kbits.p; D.kmult = s->kmult.p;
   } else { D.kbits = nullptr; D.kmult = nullptr; }
-  launch_build_kmers(D, s->stream);          // overlaps the quality upload below (side stream)
-  lap(1);
 
-  // qualities: raw_new's (uint8) round(mean quality) (containers.cpp:34) is part of the marshalling here as it is in the
-  // reference: the host pool turns the R double matrix (8 B per base, 2 GB at 10^6 uniques) into the byte matrix the
+  // The fused pass.  Qualities: raw_new's (uint8) round(mean quality) (containers.cpp:34) is part of the marshalling here as it
+  // is in the reference: the host pool turns the R double matrix (8 B per base, 2 GB at 10^6 uniques) into the byte matrix the
   // device keeps, straight into pinned memory, and each finished chunk goes out while the next is being converted.
   // NA/NaN past a read's end are never looked at (Rmain.cpp:113 copies only the first `length` entries).
   {
     const int LQ = D.LQ;
-    PinBuf<uint8_t> hq;
-    hq.alloc((size_t)nraw * LQ);
-    std::atomic<int> badq{0}, qmax{0};
+    s->up_qual.alloc((size_t)nraw * LQ);
+    // len | reads | prior of all rows side by side in pinned words (copies from the pageable vectors would be staged by the runtime
+    // on the thread that queues them)
+    const size_t n4 = ((size_t)nraw + 3) & ~(size_t)3;
+    s->up_meta.alloc(2 * n4 + n4 / 4);
+    int32_t *const m_len = s->up_meta.p;
+    uint32_t *const m_reads = (uint32_t *)(s->up_meta.p + n4);
+    uint8_t *const m_prior = (uint8_t *)(s->up_meta.p + 2 * n4);
+    const d2::MarshalRows rows{seqs, abund, priors, quals, rowlen, W2, LQ, SEQLEN, m_len, m_reads, m_prior, packed, s->up_qual.p};
+    std::mutex tally_mu;
+    d2::MarshalTally total;
+    std::atomic<int64_t> enqueue_ns{0};
     // Several samples in flight on this device (dada2hip_run_multi's threads share it: active_runs() is raised for the call): half
     // the pool per upload.  The uploads of the samples go through the pool one after the other and overlap the OTHER samples'
     // rounds, so their wall time is not what counts, the CPU time they take from the threads that feed the device is (the
@@ -416,68 +462,94 @@ void sample_create(dada2hip_sample *s, int32_t nraw, const char *const *seqs, co
     // threads, the AVX2 conversion at 185 / 359 / 272, the scalar one at 147 / 260 / 280.
     const int marshal_threads = active_runs(device).load() > 1 ? std::max(8, HostPool::get().nthreads() / 2) : 0;
     // One job over all rows (a fork-join per chunk left every thread two pieces and a barrier sixteen times over).  A chunk is
-    // whole pieces of 512 rows, about 16 MB; a countdown per chunk tells the thread that finishes its last rows, and that thread
-    // queues the chunk's copy - the copies go out in chunk order, under a lock that is taken once per chunk.
+    // whole pieces of 512 rows, about 16 MB of quality bytes (DADA2HIP_UPLOAD_CHUNK_ROWS: a test's chunk borders on a small sample);
+    // a countdown per chunk tells the thread that finishes its last rows, and that thread queues the chunk's copies - they go
+    // out in chunk order, under a lock that is taken once per chunk.
     const size_t grain = 512;
-    const size_t rows_per = std::max<size_t>(1, ((size_t)16 << 20) / (size_t)LQ / grain) * grain;
+    size_t rows_per = std::max<size_t>(1, ((size_t)16 << 20) / (size_t)LQ / grain) * grain;
+    if (knobs().upload_chunk_rows > 0) rows_per = ((size_t)std::min<long long>(knobs().upload_chunk_rows, 1ll << 30) + grain - 1) / grain * grain;
     const size_t nchunk = ((size_t)nraw + rows_per - 1) / rows_per;
     std::vector<std::atomic<int64_t>> rows_left(nchunk);
     for (size_t c = 0; c < nchunk; c++) rows_left[c].store((int64_t)std::min<size_t>(rows_per, (size_t)nraw - c * rows_per));
+    // The k-mer records of a chunk are built behind its rows' copy, while the host converts the chunks behind it (the build is
+    // 5 ms of device time at 10^6 uniques x 250 nt: queued behind the whole pass it was what the run then waited for).  A row's
+    // records depend on that row alone, and the kernel trusts a row's length: it is launched only while every row seen so far
+    // fits the stated geometry (kmer-size < length <= quals_nrow) - once one does not, the call is going to fail its checks
+    // below and no further launch is made.  What a launch on rows with another kind of input error wrote is never used.
+    std::vector<std::atomic<int>> misfit(nchunk);
+    for (size_t c = 0; c < nchunk; c++) misfit[c].store(0);
+    bool kmers_go = true;                                        // (under copy_mu)
+    int kmer_launches = 0;                                       // (under copy_mu; DADA2HIP_V2_SUMMARY and the tests read it)
     std::mutex copy_mu;
     size_t next_copy = 0;                                        // (under copy_mu) chunks [0, next_copy) have been queued
     auto chunk_done = [&]() {
       std::lock_guard<std::mutex> g(copy_mu);
+      const auto t_enq = clk::now();
       D2_HIP(hipSetDevice(device));                              // (a pool thread: the device is a per-thread setting)
       while (next_copy < nchunk && rows_left[next_copy].load() == 0) {
         const size_t r0 = next_copy * rows_per, nr = std::min<size_t>(rows_per, (size_t)nraw - r0);
-        D2_HIP(hipMemcpyAsync(D.qual + r0 * LQ, hq.p + r0 * LQ, nr * (size_t)LQ, hipMemcpyHostToDevice, s->side));
+        D2_HIP(hipMemcpyAsync(D.qual + r0 * LQ, s->up_qual.p + r0 * LQ, nr * (size_t)LQ, hipMemcpyHostToDevice, s->side));
+        D2_HIP(hipMemcpyAsync(D.seq2 + r0 * W2, packed + r0 * W2, nr * (size_t)W2 * 4, hipMemcpyHostToDevice, s->stream));
+        D2_HIP(hipMemcpyAsync(D.len + r0, m_len + r0, nr * 4, hipMemcpyHostToDevice, s->stream));
+        D2_HIP(hipMemcpyAsync(D.reads + r0, m_reads + r0, nr * 4, hipMemcpyHostToDevice, s->stream));
+        D2_HIP(hipMemcpyAsync(D.prior + r0, m_prior + r0, nr, hipMemcpyHostToDevice, s->stream));
+        if (misfit[next_copy].load()) kmers_go = false;
+        if (kmers_go) { launch_build_kmers_rows(D, (int)r0, (int)(r0 + nr), s->stream); kmer_launches++; }
         next_copy++;
       }
+      enqueue_ns += (int64_t)(ms_since(t_enq) * 1e6);
     };
+    const double ms_front = ms_since(t0);                        // (streams, buffers from the allocation cache: booked with part 2)
+    const auto t_job = clk::now();
     parallel_for((size_t)nraw, grain, [&](size_t lo, size_t hi) {
-      int mx = 0, bad = 0;
+      d2::MarshalTally t;
       for (size_t c_lo = lo; c_lo < hi;) {                       // (a piece lies in one chunk; an inline job spans them all)
         const size_t chunk = c_lo / rows_per, c_hi = std::min(hi, (chunk + 1) * rows_per);
-        for (size_t r = c_lo; r < c_hi; r++) {
-          const double *src = quals + r * (size_t)maxlen;
-          uint8_t *dst = hq.p + r * (size_t)LQ;
-          const int L = s->h_len[r];
-          // the row by hostsimd.cpp's branch-free sweep - valid for values in [0, 255.5); a row with anything else (negative,
-          // too large, NaN inside the read) is redone by the exact scalar rule
-          int row_mx = 0;
-          if (!d2::round_quality_row(src, dst, L, &row_mx)) {
-            row_mx = 0;
-            for (int p = 0; p < L; p++) {
-              const double x = src[p];
-              double xr;
-              if (x >= 0.0 && x < 256.0) { const int t = (int)x; xr = (double)(t + ((x - (double)t) >= 0.5 ? 1 : 0)); }   // round(): half away from zero
-              else xr = std::round(x);
-              if (!(xr >= 0.0 && xr <= 255.0)) { bad = 1; xr = 0.0; }
-              const int v = (int)xr;
-              row_mx = std::max(row_mx, v);
-              dst[p] = (uint8_t)v;
-            }
-          }
-          mx = std::max(mx, row_mx);
-          memset(dst + L, 0, (size_t)(LQ - L));
-        }
+        d2::MarshalTally tc;
+        d2::marshal_rows(rows, c_lo, c_hi, &tc);
+        if (tc.maxlen > rowlen || tc.maxlen >= SEQLEN || tc.minlen <= KMER_SIZE) misfit[chunk].store(1);
+        t.maxlen = std::max(t.maxlen, tc.maxlen); t.minlen = std::min(t.minlen, tc.minlen);
+        t.reads += tc.reads; t.bad_base |= tc.bad_base; t.bad_qual |= tc.bad_qual; t.qmax = std::max(t.qmax, tc.qmax);
+        // the host's own copies of the three vectors (the run and the result read them)
+        memcpy(s->h_len.data() + c_lo, m_len + c_lo, (c_hi - c_lo) * 4);
+        memcpy(s->h_reads.data() + c_lo, m_reads + c_lo, (c_hi - c_lo) * 4);
+        memcpy(s->h_prior.data() + c_lo, m_prior + c_lo, c_hi - c_lo);
         if (rows_left[chunk].fetch_sub((int64_t)(c_hi - c_lo)) == (int64_t)(c_hi - c_lo)) chunk_done();
         c_lo = c_hi;
       }
-      if (bad) badq.store(1, std::memory_order_relaxed);
-      int cur = qmax.load();
-      while (mx > cur && !qmax.compare_exchange_weak(cur, mx)) {}
+      std::lock_guard<std::mutex> g(tally_mu);                   // (once per piece)
+      total.maxlen = std::max(total.maxlen, t.maxlen); total.minlen = std::min(total.minlen, t.minlen);
+      total.reads += t.reads; total.bad_base |= t.bad_base; total.bad_qual |= t.bad_qual; total.qmax = std::max(total.qmax, t.qmax);
     }, marshal_threads);
-    if (next_copy != nchunk) throw RuntimeErr{DADA2HIP_ERR_RUNTIME, "dada2hip: quality upload left a chunk behind"};
-    lap(2);
-    D2_HIP(hipStreamSynchronize(s->side));                    // (the pinned buffer goes back to the cache)
-    lap(3);
-    if (badq.load()) throw InputError{"Invalid derep$quals matrix. Quality values must be positive integers."};
-    s->qmax = qmax.load();
+    if (next_copy != nchunk) throw RuntimeErr{DADA2HIP_ERR_RUNTIME, "dada2hip: the upload left a chunk behind"};
+    // (in front of the checks: the line of a call that is about to fail says how many launches its rows were given)
+    if (knobs().v2_summary)
+      fprintf(stderr, "[upload] rows %d  chunk rows %zu  chunks %zu  k-mer launches %d\n", (int)nraw, rows_per, nchunk, kmer_launches);
+    s->ms_upload_part[0] = (double)enqueue_ns.load() * 1e-6;
+    s->ms_upload_part[1] = ms_since(t_job); s->ms_upload_part[2] = ms_front; t_lap = clk::now();
+    maxlen = total.maxlen; minlen = total.minlen;
+    s->total_reads = total.reads;
+    // the input errors, in the order they have always been raised in; what the copies above carried to the device is never used
+    check_lengths();
+    if (!kmers_go) throw RuntimeErr{DADA2HIP_ERR_RUNTIME, "dada2hip: a row outside the stated geometry passed the checks"};
+    if (total.bad_base) throw InputError{"Invalid derep$uniques vector. Sequences must be made up only of A/C/G/T."};
+    if (total.bad_qual) throw InputError{"Invalid derep$quals matrix. Quality values must be positive integers."};
+    D.minlen = minlen;
+    s->qmax = total.qmax;
   }
-  D2_HIP(hipStreamSynchronize(s->stream));
-  D2_HIP(hipGetLastError());
-  lap(4);
+  // whatever is queued on the main stream from here on - the run - follows the qualities, without the host waiting for them
+  if (!s->ev_up) D2_HIP(hipEventCreateWithFlags(&s->ev_up, hipEventDisableTiming));
+  D2_HIP(hipEventRecord(s->ev_up, s->side));
+  D2_HIP(hipStreamWaitEvent(s->stream, s->ev_up, 0));
+  s->ms_upload_part[2] += ms_since(t_lap); t_lap = clk::now();
+  if (!defer) {
+    D2_HIP(hipStreamSynchronize(s->side));
+    lap(3);
+    D2_HIP(hipStreamSynchronize(s->stream));
+    D2_HIP(hipGetLastError());
+    lap(4);
+    s->up_qual.free(); s->up_meta.free();                       // (the pinned sources go back to the cache)
+  }
   s->ms_upload = ms_since(t0);
 }
 
@@ -854,7 +926,10 @@ struct Run {
     D2_HIP(hipMemcpyAsync(d_thresh_one.p, thresh_one.data(), thresh_one.size() * 4, hipMemcpyHostToDevice, stq));
     D2_HIP(hipMemcpyAsync(d_thresh_round.p, thresh_round.data(), thresh_round.size() * 4, hipMemcpyHostToDevice, stq));
     const double ms_as_enq = ms_since(t_as);
-    D2_HIP(hipStreamSynchronize(stq));                           // the threshold vectors may be rebuilt by the next run
+    // the threshold vectors may be rebuilt by the next run.  sample_run relies on this wait too: it releases the pinned sources
+    // of a boundary call's upload (up_qual, up_meta) right behind alloc_state, and the copies that read them are in front of it
+    // in this stream (or ordered in front of it by ev_up) - a change that drops the wait must move that release
+    D2_HIP(hipStreamSynchronize(stq));
     if (knobs().v2_summary) fprintf(stderr, "[run] alloc_state: buffers %.2f ms, + clears enqueued %.2f, + stream drained %.2f\n", ms_as_alloc, ms_as_enq, ms_since(t_as));
   }
 
@@ -2418,6 +2493,7 @@ void sample_run(dada2hip_sample *s, const double *err, int err_ncol, const dada2
   hipStream_t stq = s->stream;
   lap(1);
   run.alloc_state();
+  s->up_qual.free(); s->up_meta.free();   // (a boundary call's upload: alloc_state has waited for the stream, and the stream for the side stream's copies)
   lap(2);
   // b_init (containers.cpp:111-137): one partition holding every unique, centre = first max-reads member
   run.clust_of.assign(N, 0);
@@ -2454,8 +2530,8 @@ void sample_run(dada2hip_sample *s, const double *err, int err_ncol, const dada2
     fprintf(stderr, "[run] setup %.2f ms: aligner ring / run cache %.2f  init_run %.2f  alloc_state %.2f  b_init mirror %.2f  v2_alloc %.2f\n", run.st.ms_setup,
             t_sub[0], t_sub[1], t_sub[2], t_sub[3], t_sub[4]);
   if (knobs().v2_summary)
-    fprintf(stderr, "[run] upload %.2f ms: lengths %.2f  packing %.2f  quality conversion %.2f  wait side stream %.2f  wait main stream %.2f\n",
-            s->ms_upload, s->ms_upload_part[0], s->ms_upload_part[1], s->ms_upload_part[2], s->ms_upload_part[3], s->ms_upload_part[4]);
+    fprintf(stderr, "[run] upload %.2f ms: fused pass %.2f (enqueue of its copies and k-mer launches %.2f)  buffers + checks %.2f  wait side stream %.2f  wait main stream %.2f\n",
+            s->ms_upload, s->ms_upload_part[1], s->ms_upload_part[0], s->ms_upload_part[2], s->ms_upload_part[3], s->ms_upload_part[4]);
   const auto t_round0 = clk::now();
   run.compare_round(0, (int)run.bi[0].center, 1.0);   // Rmain.cpp:309-310: no k-mer screen in round 0
   run.st.ms_round0 = ms_since(t_round0);
@@ -2526,7 +2602,21 @@ void sample_run(dada2hip_sample *s, const double *err, int err_ncol, const dada2
   uint64_t n_final_local = 0;
   run.f_centres.alloc((size_t)C);
   for (int i = 0; i < C; i++) run.f_centres.p[i] = (int32_t)run.bi[i].center;
-  if (!shard) {
+  // The list is built on the device (k_final_worklist: a counting sort of the uniques by partition, queued here, directly behind the
+  // last round) unless the run is sharded (a rank lists the members of its own block) or the scratch of the sort - a count per
+  // tile of 1 024 uniques and partition - would pass 64 MB.  The host only sums the padded sizes: the launches need them.  The
+  // order inside a partition differs from the host-built list's (ascending uniques, not list order); nothing reads it - d_view is
+  // indexed by unique, the tables are exact integer sums, the representative comes from slot_of.
+  DevBuf<int32_t> d_fwl_tcount, d_fwl_size, d_fwl_off;
+  size_t dev_tot = 0;
+  for (int i = 0; i < C; i++) dev_tot += (run.bi[i].raw.size() + per - 1) / per * per;
+  const bool dev_list = !shard && dev_tot > 0 && dev_tot < ((size_t)1 << 31) &&
+                        (size_t)final_worklist_tiles(N) * (size_t)C <= ((size_t)16 << 20);
+  if (dev_list) {
+    for (int i = 0; i < C; i++) n_final_local += run.bi[i].raw.size();
+    nwork = dev_tot; nchunk = dev_tot / per;
+    run.f_work.alloc(per); run.f_cc.alloc(1);
+  } else if (!shard) {
     // every member of every partition, a partition's members in list order, padded to whole chunks: the member lists ARE the
     // work list (one block copy per partition instead of a push per unique: 10^6 uniques cost 5 ms here)
     size_t tot = 0;
@@ -2565,6 +2655,12 @@ void sample_run(dada2hip_sample *s, const double *err, int err_ncol, const dada2
   }
   if (nwork == 0) { std::fill(run.f_work.p, run.f_work.p + per, -1); run.f_cc.p[0] = (int32_t)run.bi[0].center; nwork = per; nchunk = 1; }
   s->d_work.alloc(nwork); s->d_chunk_centre.alloc(nchunk);
+  s->fin_nwork = (int64_t)nwork; s->fin_nchunk = (int64_t)nchunk; s->fin_per = (int32_t)per; s->fin_on_device = dev_list ? 1 : 0;
+  if (dev_list) {
+    d_fwl_tcount.alloc((size_t)final_worklist_tiles(N) * (size_t)C); d_fwl_size.alloc(C); d_fwl_off.alloc(C);
+    launch_final_worklist(run.P.clust_of, run.P.centre_of, N, C, (int)per, d_fwl_tcount.p, d_fwl_size.p, d_fwl_off.p, s->d_work.p,
+                          (int)nwork, s->d_chunk_centre.p, stq);
+  }
   s->d_view.alloc((size_t)N * LV);
   s->d_correct.alloc(N);
   s->d_trans.alloc((size_t)16 * err_ncol); s->d_nsubs.alloc(N);
@@ -2589,8 +2685,10 @@ void sample_run(dada2hip_sample *s, const double *err, int err_ncol, const dada2
     D2_HIP(hipMemcpyAsync(run.f_pcls.p, d_bcls.p, (size_t)nb, hipMemcpyDeviceToHost, s->side));
   }
 
-  D2_HIP(hipMemcpyAsync(s->d_work.p, run.f_work.p, nwork * 4, hipMemcpyHostToDevice, stq));
-  D2_HIP(hipMemcpyAsync(s->d_chunk_centre.p, run.f_cc.p, nchunk * 4, hipMemcpyHostToDevice, stq));
+  if (!dev_list) {
+    D2_HIP(hipMemcpyAsync(s->d_work.p, run.f_work.p, nwork * 4, hipMemcpyHostToDevice, stq));
+    D2_HIP(hipMemcpyAsync(s->d_chunk_centre.p, run.f_cc.p, nchunk * 4, hipMemcpyHostToDevice, stq));
+  }
   if (opts->band_size == 0) {
     launch_gapless(D, 0, s->d_chunk_centre.p, s->d_work.p, nullptr, (int)nwork, run.ap, s->d_err.p, s->d_lambda.p,
                    s->d_ham.p, s->d_view.p, LV, 0, stq);
@@ -3013,12 +3111,19 @@ int dada2hip_sample_run_sharded(dada2hip_sample *s, const double *err, int32_t e
 
 void dada2hip_sample_free(dada2hip_sample *s) {
   if (!s) return;
+  const auto t_free = clk::now();
   if (s->stream) { (void)hipSetDevice(s->device); (void)hipStreamSynchronize(s->stream); (void)hipStreamDestroy(s->stream); }
   if (s->cmp) { (void)hipStreamSynchronize(s->cmp); (void)hipStreamDestroy(s->cmp); }
   if (s->side) { (void)hipStreamSynchronize(s->side); (void)hipStreamDestroy(s->side); }   // (its buffers return to the allocation cache)
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
+  if (s->ev_up) (void)hipEventDestroy(s->ev_up);
+  const double ms_streams = ms_since(t_free);
+  const bool had_run = (bool)s->run_cache;
   delete s;
+  // (DADA2HIP_V2_SUMMARY: the teardown of a sample that was run, outside every other clock - the Run object and the sample's
+  //  buffers go back to the allocation cache, the host vectors to the allocator)
+  if (had_run && knobs().v2_summary) fprintf(stderr, "[run] teardown %.2f ms: streams + events %.2f  delete sample (Run, buffers, vectors) %.2f\n", ms_since(t_free), ms_streams, ms_since(t_free) - ms_streams);
 }
 
 int32_t dada2hip_sample_nraw(const dada2hip_sample *s) { return s ? s->D.N : 0; }
@@ -3040,9 +3145,11 @@ int dada2hip_dada_uniques(int32_t nraw, const char *const *seqs, const int32_t *
                           char *errbuf, size_t errlen) {
   if (out) *out = nullptr;
   if (nraw > 0 && seqs && abundances && priors == nullptr) { /* priors optional */ }
-  dada2hip_sample *s = nullptr;
-  int rc = dada2hip_sample_create(nraw, seqs, abundances, priors, quals, quals_nrow, device, &s, errbuf, errlen);
-  if (rc != DADA2HIP_OK) return rc;
+  // (the sample is run at once: its upload need not be over between the two - sample_create's deferred form.  A HIP error of the
+  //  upload surfaces from the run's first wait, as the same error class.)
+  dada2hip_sample *s = new dada2hip_sample();
+  int rc = guarded(errbuf, errlen, [&] { sample_create(s, nraw, seqs, abundances, priors, quals, quals_nrow, device, /*lite=*/false, /*defer=*/true); });
+  if (rc != DADA2HIP_OK) { dada2hip_sample_free(s); return rc; }
   rc = dada2hip_sample_run(s, err, err_ncol, opts, hooks, out, errbuf, errlen);
   dada2hip_sample_free(s);
   return rc;
@@ -3185,6 +3292,20 @@ int32_t dada2hip_launch_ledger(uint64_t *mask, int32_t nwords, int32_t clear) {
 }
 
 int32_t dada2hip_nw_ring_trips(int32_t clear) { return nw_trips_read(clear != 0); }
+
+int dada2hip_sample_final_worklist(dada2hip_sample *s, int32_t *work, int64_t work_cap, int32_t *chunk_centre, int64_t chunk_cap,
+                                   int64_t *info, char *errbuf, size_t errlen) {
+  return guarded(errbuf, errlen, [&] {
+    if (!s || !info) throw InputError{"dada2hip: no sample."};
+    select_device(s->device);
+    info[0] = s->fin_nwork; info[1] = s->fin_nchunk; info[2] = s->fin_per; info[3] = s->fin_on_device;
+    if (s->fin_nwork <= 0 || !s->d_work.p || !s->d_chunk_centre.p) throw InputError{"dada2hip: the sample has not been run."};
+    D2_HIP(hipStreamSynchronize(s->stream));
+    if (work && work_cap >= s->fin_nwork) D2_HIP(hipMemcpy(work, s->d_work.p, (size_t)s->fin_nwork * 4, hipMemcpyDeviceToHost));
+    if (chunk_centre && chunk_cap >= s->fin_nchunk)
+      D2_HIP(hipMemcpy(chunk_centre, s->d_chunk_centre.p, (size_t)s->fin_nchunk * 4, hipMemcpyDeviceToHost));
+  });
+}
 
 int dada2hip_calc_pA(int32_t n, const int32_t *reads, const double *E_reads, const uint8_t *prior, int32_t device,
                      double *out, char *errbuf, size_t errlen) {

@@ -136,6 +136,12 @@ void launch_fill_f64(double *d_p, size_t n, double v, hipStream_t st);
 void launch_fill_null(int n, const uint8_t *d_cls, double *d_lam, uint32_t *d_ham, hipStream_t st);
 // d_out[d_key[i]] = i, i < n (keys outside [0, n_out) are left out); the caller presets d_out
 void launch_scatter_index(const int32_t *d_key, int n, int32_t *d_out, int n_out, hipStream_t st);
+// The final pass's work list on the device (kernels.hip, k_final_worklist): d_work[nwork] = partitions in index order, each padded
+// with -1 to whole chunks of `per`, members in ascending unique order; d_chunk_centre[nwork / per].  Scratch: d_tcount
+// [final_worklist_tiles(n) * C], d_size[C], d_off[C].  nwork is the host's sum of the padded partition sizes.
+int final_worklist_tiles(int n);
+void launch_final_worklist(const int32_t *d_clust_of, const int32_t *d_centre_of, int n, int C, int per, int32_t *d_tcount,
+                           int32_t *d_size, int32_t *d_off, int32_t *d_work, int nwork, int32_t *d_chunk_centre, hipStream_t st);
 void launch_store(const PartState &P, const SampleDev &S, int ci, int centre, double total_reads, const double *d_lam,
                   const uint32_t *d_ham, const int32_t *d_round_counters, const uint8_t *d_cls, int32_t *d_zero2, hipStream_t st);
 // The store filter of a round (ci >= 1) rides in front of the round's first shuffle: pass its arguments here.
@@ -199,6 +205,7 @@ void launch_posthoc(const PartState &P, const SampleDev &S, const int32_t *d_clu
 
 // launch wrappers implemented in kernels.hip -----------------------------------------------------
 void launch_build_kmers(const SampleDev &S, hipStream_t st);
+void launch_build_kmers_rows(const SampleDev &S, int r0, int r1, hipStream_t st);   // the records of uniques [r0, r1) only
 // counters: [0]=#NW work items, [1]=#gapless work items, [2]=#shrouded, [3]=#skipped
 void launch_screen(const SampleDev &S, int centre, const ScreenParams &sp, const uint8_t *d_skip, const uint8_t *d_lock,
                    int greedy, const int32_t *d_thresh, uint8_t *d_cls, double *d_lambda, uint32_t *d_ham, int32_t *d_nw_list,

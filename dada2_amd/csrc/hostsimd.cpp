@@ -4,8 +4,13 @@
 // compilation).  Each loop has a scalar form that is the rule, and an explicit AVX2 form (the compiler vectorises neither: the
 // double -> byte conversion with its range test comes out as one vcvttsd2si and one branch per element); which one serves is
 // decided once, at load, from the CPU.  tools/host_marshal.cpp times and checks every form against the scalar rule.
+// marshal_rows (marshal.h) is the row work of the boundary's fused upload pass built from the two: length, abundance, prior,
+// packing and rounding of a row in one visit; tools/upload_fused_check.cpp runs it under the host sanitizers.
+#include <cmath>
 #include <cstdint>
 #include <cstring>
+
+#include "marshal.h"
 
 #if defined(__x86_64__)
 #include <immintrin.h>
@@ -169,5 +174,40 @@ const Chosen chosen;
 
 bool round_quality_row(const double *src, uint8_t *dst, int L, int *mx_out) { return chosen.r(src, dst, L, mx_out); }
 uint32_t pack_row_2bit(const char *q, int len, uint32_t *row, int W2) { return chosen.p(q, len, row, W2); }
+
+// ---- the fused upload pass: everything the boundary does to a row, in one visit (marshal.h) --------------------------------
+void marshal_rows(const MarshalRows &m, size_t lo, size_t hi, MarshalTally *t) {
+  for (size_t i = lo; i < hi; i++) {
+    const int l = (int)strnlen(m.seqs[i], (size_t)m.len_cap + 1);
+    m.len[i] = l;
+    t->maxlen = l > t->maxlen ? l : t->maxlen;
+    t->minlen = l < t->minlen ? l : t->minlen;
+    m.reads[i] = (uint32_t)m.abund[i];
+    t->reads += (uint32_t)m.abund[i];
+    m.prior[i] = m.priors && m.priors[i] ? 1 : 0;
+    if (l > m.stride || l >= m.len_cap) continue;                  // (an input error: the caller raises it, the row is only recorded)
+    t->bad_base |= pack_row_2bit(m.seqs[i], l, m.packed + i * (size_t)m.W2, m.W2);
+    const double *src = m.quals + i * (size_t)m.stride;
+    uint8_t *dst = m.qbytes + i * (size_t)m.LQ;
+    // the row by the branch-free sweep - valid for values in [0, 255.5); a row with anything else (negative, too large, NaN
+    // inside the read) is redone by the exact scalar rule
+    int row_mx = 0;
+    if (!round_quality_row(src, dst, l, &row_mx)) {
+      row_mx = 0;
+      for (int p = 0; p < l; p++) {
+        const double x = src[p];
+        double xr;
+        if (x >= 0.0 && x < 256.0) { const int v = (int)x; xr = (double)(v + ((x - (double)v) >= 0.5 ? 1 : 0)); }   // round(): half away from zero
+        else xr = std::round(x);
+        if (!(xr >= 0.0 && xr <= 255.0)) { t->bad_qual = 1; xr = 0.0; }
+        const int v = (int)xr;
+        row_mx = v > row_mx ? v : row_mx;
+        dst[p] = (uint8_t)v;
+      }
+    }
+    t->qmax = row_mx > t->qmax ? row_mx : t->qmax;
+    memset(dst + l, 0, (size_t)(m.LQ - l));
+  }
+}
 
 }  // namespace d2

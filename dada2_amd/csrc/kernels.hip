@@ -58,14 +58,16 @@ static __device__ __forceinline__ uint32_t homo_at(const uint32_t *__restrict__ 
 // count tables (kmers.cpp:13-93) is   sum_k min(a_k, b_k) = #{ i : rank_i < count_centre[kmer_i] },
 // so a round streams ~2 B/position instead of the 1 KiB count table per unique; k-mers that occur
 // more than 63 times go to a small per-unique "heavy" list and are corrected exactly.
-__global__ __launch_bounds__(64) void k_build_kmers(SampleDev S) {
+// Rows [r0, r1): a unique's records depend on its own row alone, so the boundary's upload builds them chunk by chunk, each
+// chunk behind its rows' copy, while the host is still converting the chunks behind it (driver.cpp, sample_create).
+__global__ __launch_bounds__(64) void k_build_kmers(SampleDev S, int r0, int r1) {
   __shared__ uint16_t tbl[NKMER * 64];
   const int lane = threadIdx.x;
   uint16_t *t = tbl + lane;
-  for (int base = blockIdx.x * 64; base < S.N; base += gridDim.x * 64) {
+  for (int base = r0 + blockIdx.x * 64; base < r1; base += gridDim.x * 64) {
     const int r = base + lane;
     for (int k = 0; k < NKMER; k++) t[k * 64] = 0;
-    if (r < S.N) {
+    if (r < r1) {
       const uint32_t *row = S.seq2 + (size_t)r * S.W2;
       uint16_t *ko = S.kord + (size_t)r * S.LK;
       const int L = S.len[r], nk = L - KMER_SIZE + 1;
@@ -99,10 +101,12 @@ __global__ __launch_bounds__(64) void k_build_kmers(SampleDev S) {
   }
 }
 
-void launch_build_kmers(const SampleDev &S, hipStream_t st) {
-  int grid = std::min((S.N + 63) / 64, 1024);
-  hipLaunchKernelGGL(k_build_kmers, dim3(grid), dim3(64), 0, st, S);
+void launch_build_kmers_rows(const SampleDev &S, int r0, int r1, hipStream_t st) {
+  if (r0 < 0 || r1 > S.N || r0 >= r1) return;
+  int grid = std::min((r1 - r0 + 63) / 64, 1024);
+  hipLaunchKernelGGL(k_build_kmers, dim3(grid), dim3(64), 0, st, S, r0, r1);
 }
+void launch_build_kmers(const SampleDev &S, hipStream_t st) { launch_build_kmers_rows(S, 0, S.N, st); }
 
 // ------------------------------------------------------------------------------------------------
 // Centre record of a round, built once by one block so the screen blocks only copy ~3.5 KB out of L2:
@@ -2629,6 +2633,98 @@ void launch_scatter_index(const int32_t *d_key, int n, int32_t *d_out, int n_out
   if (n <= 0) return;
   hipLaunchKernelGGL(k_scatter_index, dim3((n + 255) / 256), dim3(256), 0, st, d_key, n, d_out, n_out);
 }
+
+// ------------------------------------------------------------------------------------------------
+// The final pass's work list, built on the device from the partition of every unique (driver.cpp, "final alignments"):
+// partitions in index order, each padded with -1 to whole chunks of `per` slots, one centre per chunk, a partition's members in
+// ascending unique order (stable: two runs of a build give the same list).  A counting sort by tiles of FWL_TILE uniques:
+//   count    tcount[tile][c] = members of partition c in the tile            (block per tile, atomics on the tile's own row)
+//   prefix   per partition: the counts become exclusive prefixes over the tiles, size[c] their sum      (thread per partition)
+//   offsets  off[c] = exclusive scan of the padded sizes                      (one block)
+//   scatter  unique r of partition c goes to off[c] + (prefix of its tile) + (members of c in front of it in the tile); the
+//            member at rank k * per writes chunk k's centre                   (block per tile, 256 uniques at a time, in order)
+constexpr int FWL_TILE = 1024;
+__global__ __launch_bounds__(256) void k_final_worklist_count(const int32_t *__restrict__ clust_of, int n, int C, int32_t *__restrict__ tcount) {
+  const size_t row = (size_t)blockIdx.x * (size_t)C;
+  for (int k = threadIdx.x; k < FWL_TILE; k += 256) {
+    const int r = blockIdx.x * FWL_TILE + k;
+    if (r >= n) break;
+    const int c = clust_of[r];
+    if ((uint32_t)c < (uint32_t)C) atomicAdd(&tcount[row + (size_t)c], 1);
+  }
+}
+__global__ __launch_bounds__(256) void k_final_worklist_prefix(int32_t *__restrict__ tcount, int ntiles, int C, int32_t *__restrict__ size) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  int32_t run = 0;
+  for (int t = 0; t < ntiles; t++) {
+    int32_t *p = tcount + (size_t)t * (size_t)C + (size_t)c;
+    const int32_t v = *p;
+    *p = run;
+    run += v;
+  }
+  size[c] = run;
+}
+__global__ __launch_bounds__(1024) void k_final_worklist_offsets(const int32_t *__restrict__ size, int C, int per, int32_t *__restrict__ off) {
+  __shared__ int32_t part[1024];
+  const int span = (C + 1023) / 1024, lo = min(C, (int)threadIdx.x * span), hi = min(C, lo + span);
+  int32_t sum = 0;
+  for (int c = lo; c < hi; c++) sum += (size[c] + per - 1) / per * per;
+  part[threadIdx.x] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int32_t run = 0;
+    for (int i = 0; i < 1024; i++) { const int32_t v = part[i]; part[i] = run; run += v; }
+  }
+  __syncthreads();
+  int32_t run = part[threadIdx.x];
+  for (int c = lo; c < hi; c++) { off[c] = run; run += (size[c] + per - 1) / per * per; }
+}
+__global__ __launch_bounds__(256) void k_final_worklist(const int32_t *__restrict__ clust_of, const int32_t *__restrict__ centre_of, int n, int C,
+                                                        int per, int32_t *tcount, const int32_t *__restrict__ off, int32_t *__restrict__ work,
+                                                        int nwork, int32_t *__restrict__ chunk_centre) {
+  __shared__ int32_t cs[256];
+  const int tid = threadIdx.x;
+  volatile int32_t *row = tcount + (size_t)blockIdx.x * (size_t)C;   // this tile's running ranks: read, then advanced, by this block alone
+  for (int sub = 0; sub < FWL_TILE / 256; sub++) {
+    const int r = blockIdx.x * FWL_TILE + sub * 256 + tid;
+    int c = -1;
+    if (r < n) { c = clust_of[r]; if ((uint32_t)c >= (uint32_t)C) c = -1; }
+    cs[tid] = c;
+    __syncthreads();
+    int rank = 0;
+    bool last = false;
+    if (c >= 0) {
+      int before = 0;
+      for (int j = 0; j < tid; j++) before += cs[j] == c;
+      last = true;
+      for (int j = tid + 1; j < 256; j++) if (cs[j] == c) { last = false; break; }
+      rank = row[c] + before;
+      const int pos = off[c] + rank;
+      if (pos >= 0 && pos < nwork) {
+        work[pos] = r;
+        if (rank % per == 0) chunk_centre[pos / per] = centre_of[c];
+      }
+    }
+    __syncthreads();                    // every rank of this step has been read
+    if (last) row[c] = rank + 1;        // the partition's last member of the step: where the next step's members go on
+    __threadfence_block();
+    __syncthreads();
+  }
+}
+void launch_final_worklist(const int32_t *d_clust_of, const int32_t *d_centre_of, int n, int C, int per, int32_t *d_tcount,
+                           int32_t *d_size, int32_t *d_off, int32_t *d_work, int nwork, int32_t *d_chunk_centre, hipStream_t st) {
+  if (n <= 0 || C <= 0 || per <= 0 || nwork <= 0) return;
+  const int ntiles = (n + FWL_TILE - 1) / FWL_TILE;
+  D2_HIP(hipMemsetAsync(d_tcount, 0, (size_t)ntiles * (size_t)C * 4, st));
+  D2_HIP(hipMemsetAsync(d_work, 0xFF, (size_t)nwork * 4, st));                   // -1: the padding
+  hipLaunchKernelGGL(k_final_worklist_count, dim3(ntiles), dim3(256), 0, st, d_clust_of, n, C, d_tcount);
+  hipLaunchKernelGGL(k_final_worklist_prefix, dim3((C + 255) / 256), dim3(256), 0, st, d_tcount, ntiles, C, d_size);
+  hipLaunchKernelGGL(k_final_worklist_offsets, dim3(1), dim3(1024), 0, st, d_size, C, per, d_off);
+  hipLaunchKernelGGL(k_final_worklist, dim3(ntiles), dim3(256), 0, st, d_clust_of, d_centre_of, n, C, per, d_tcount, d_off, d_work, nwork,
+                     d_chunk_centre);
+}
+int final_worklist_tiles(int n) { return (n + FWL_TILE - 1) / FWL_TILE; }
 
 void launch_store(const PartState &P, const SampleDev &S, int ci, int centre, double total_reads, const double *d_lam,
                   const uint32_t *d_ham, const int32_t *d_round_counters, const uint8_t *d_cls, int32_t *d_zero2, hipStream_t st) {

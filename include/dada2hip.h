@@ -52,6 +52,8 @@
  *   DADA2HIP_NW_KERNEL=lane|coop|wide  force one aligner family;  DADA2HIP_AD_HOMO=0  homopolymer gaps on the lane kernels
  *   DADA2HIP_NW_RING=<n>               waves of the lane aligners' scratch ring (a multiple of 4, at least 4; default and at most
  *                                      the automatic size: 4 096 waves, halved down to 64 while the pointers would pass 6 GiB)
+ *   DADA2HIP_UPLOAD_CHUNK_ROWS=<n>     rows per chunk of the boundary's upload (rounded up to a multiple of 512; default: about 16 MB of
+ *                                      quality bytes; tests: chunk borders on small samples)
  *   DADA2HIP_WAIT=block, DADA2HIP_WAIT_TIMEOUT_S=<s>   sleep instead of spin while waiting; bound of every device wait
  *   DADA2HIP_HOST_THREADS=<n>, DADA2HIP_ALLOC_CACHE=0, DADA2HIP_ALLOC_CACHE_GB=<n>   marshalling pool, allocation cache
  *   DADA2HIP_DEREP_INFLATE=zlib        dada2hip_derep_fastq, dada2hip_filter_fastq: .gz files through zlib's streaming inflate even where libdeflate is installed
@@ -920,6 +922,13 @@ int32_t dada2hip_launch_ledger(uint64_t *mask, int32_t nwords, int32_t clear);
  * screen off, the number of uniques where the device counts the work.  1: every wave had one chunk at most; from 2 on a wave
  * went back to the slot of the scratch ring it had used (DADA2HIP_NW_RING makes the ring small).  Clears when clear != 0. */
 int32_t dada2hip_nw_ring_trips(int32_t clear);
+
+/* Diagnostic (tests): the work list of the sample's last run's final pass as it lies on the device - `work`: partitions in index
+ * order, each padded with -1 to whole chunks of `per` slots; `chunk_centre`: one centre per chunk.  info[0..3] = slots, chunks, per,
+ * 1 if the list was built on the device (0: by the host - a sharded run, or the scratch of the device's sort too large).  An
+ * array is filled only if its capacity (in entries) holds it: call with nulls for the sizes first.  No effect on any result. */
+int dada2hip_sample_final_worklist(dada2hip_sample *s, int32_t *work, int64_t work_cap, int32_t *chunk_centre, int64_t chunk_cap,
+                                   int64_t *info, char *errbuf, size_t errlen);
 
 /* Poisson tail used for the abundance p-value: calc_pA (src/pval.cpp:44-64) evaluated by the
  * device kernel for n (reads, E) pairs — for parity tests against the oracle. */
