@@ -113,6 +113,7 @@ EXPORTS = [
     "dada2hip_result_bs_clust", "dada2hip_result_subqual", "dada2hip_result_clusterquals", "dada2hip_result_map",
     "dada2hip_result_pval", "dada2hip_result_stats", "dada2hip_result_free", "dada2hip_nwalign", "dada2hip_nwvec",
     "dada2hip_sample_compare", "dada2hip_launch_ledger", "dada2hip_nw_ring_trips", "dada2hip_sample_final_worklist", "dada2hip_calc_pA", "dada2hip_version", "dada2hip_run_multi", "dada2hip_trim_cache",
+    "dada2hip_alloc_poison_stats",
     "dada2hip_table_bimera2", "dada2hip_is_bimera", "dada2hip_bimera_pairs", "dada2hip_derep_fastq", "dada2hip_derep_nuniques",
     "dada2hip_derep_nreads", "dada2hip_derep_maxlen", "dada2hip_derep_seqs", "dada2hip_derep_abundances",
     "dada2hip_derep_quals", "dada2hip_derep_map", "dada2hip_derep_free", "dada2hip_sample_from_derep",
@@ -446,6 +447,8 @@ def lib():
                                                      C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), vp, cp, C.c_size_t]
     L.dada2hip_trim_cache.argtypes = []
     L.dada2hip_trim_cache.restype = None
+    L.dada2hip_alloc_poison_stats.argtypes = [C.POINTER(C.c_int64)]
+    L.dada2hip_alloc_poison_stats.restype = None
     _lib = L
     return L
 

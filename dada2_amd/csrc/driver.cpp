@@ -64,7 +64,10 @@ template <typename T> struct DevBuf {
     n = count;
     // 64 bytes of slack behind the last element: the streaming kernels read 16 bytes per lane and their last lane may start
     // inside the array and end behind it (what it reads there is never used)
-    D2_HIP(AllocCache::get().dev_alloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T) + 64));
+    const hipError_t e = AllocCache::get().dev_alloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T) + 64);
+    if (e == hipErrorNotReady)   // (DADA2HIP_ALLOC_POISON: the fill of the block did not end within the bound on device waits)
+      throw d2::DeviceError{DADA2HIP_ERR_DEVICE, "dada2hip: timed out waiting for the device (allocation fill)"};
+    D2_HIP(e);
   }
   void zero(hipStream_t st) { D2_HIP(hipMemsetAsync(p, 0, n * sizeof(T), st)); }
   void free() { if (p) AllocCache::get().dev_release(p); p = nullptr; n = 0; }
@@ -3213,6 +3216,7 @@ int dada2hip_run_multi(int32_t n_samples, const dada2hip_sample_input *samples, 
 }
 
 void dada2hip_trim_cache(void) { AllocCache::get().trim(); }
+void dada2hip_alloc_poison_stats(int64_t out[4]) { AllocCache::get().poison_stats(out); }
 
 int dada2hip_sample_compare(dada2hip_sample *s, int32_t centre, const double *err, int32_t err_ncol,
                             const dada2hip_opts *opts, double kdist_cutoff, const uint8_t *skip, double *lambda,

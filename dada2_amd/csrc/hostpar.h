@@ -5,7 +5,9 @@
 // hipHostMalloc again ("no global state except an optional per-device context cache").
 #pragma once
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -180,6 +182,7 @@ class AllocCache {
     int dev = 0;
     (void)hipGetDevice(&dev);
     const size_t cls = alloc_class(bytes);
+    bool hit = false;
     {
       std::lock_guard<std::mutex> g(mu_);
       auto &fl = dev_free_[dev];
@@ -189,9 +192,10 @@ class AllocCache {
         fl.erase(it);
         dev_cached_ -= cls;
         dev_live_[*p] = {dev, cls};
-        return hipSuccess;
+        hit = true;
       }
     }
+    if (hit) return dev_poison(dev, *p, cls);
     hipError_t e = hipMalloc(p, cls);
     if (e != hipSuccess) {   // out of memory: give the cache back and retry once
       trim();
@@ -199,9 +203,11 @@ class AllocCache {
       e = hipMalloc(p, cls);
       if (e != hipSuccess) return e;
     }
-    std::lock_guard<std::mutex> g(mu_);
-    dev_live_[*p] = {dev, cls};
-    return hipSuccess;
+    {
+      std::lock_guard<std::mutex> g(mu_);
+      dev_live_[*p] = {dev, cls};
+    }
+    return dev_poison(dev, *p, cls);
   }
   void dev_release(void *p) {
     if (!p) return;
@@ -219,6 +225,7 @@ class AllocCache {
   }
   hipError_t pin_alloc(void **p, size_t bytes) {
     const size_t cls = alloc_class(bytes);
+    bool hit = false;
     {
       std::lock_guard<std::mutex> g(mu_);
       auto it = pin_free_.find(cls);
@@ -227,14 +234,27 @@ class AllocCache {
         pin_free_.erase(it);
         pin_cached_ -= cls;
         pin_live_[*p] = cls;
-        return hipSuccess;
+        hit = true;
       }
     }
-    hipError_t e = hipHostMalloc(p, cls, hipHostMallocDefault);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> g(mu_);
-    pin_live_[*p] = cls;
+    if (!hit) {
+      hipError_t e = hipHostMalloc(p, cls, hipHostMallocDefault);
+      if (e != hipSuccess) return e;
+      std::lock_guard<std::mutex> g(mu_);
+      pin_live_[*p] = cls;
+    }
+    const int v = knobs().alloc_poison;
+    if (v >= 0) {
+      std::memset(*p, v, cls);
+      poison_[2].fetch_add(1, std::memory_order_relaxed);
+      poison_[3].fetch_add((int64_t)cls, std::memory_order_relaxed);
+    }
     return hipSuccess;
+  }
+  // DADA2HIP_ALLOC_POISON (dada2hip_alloc_poison_stats): device blocks / device bytes / pinned blocks / pinned bytes filled since
+  // the process started
+  void poison_stats(int64_t out[4]) {
+    for (int i = 0; i < 4; i++) out[i] = poison_[i].load(std::memory_order_relaxed);
   }
   void pin_release(void *p) {
     if (!p) return;
@@ -274,6 +294,61 @@ class AllocCache {
     if (knobs().alloc_cache_gb >= 0) cap_ = (size_t)knobs().alloc_cache_gb << 30;
   }
   struct Blk { int dev; size_t cls; };
+  // DADA2HIP_ALLOC_POISON=<byte> (test knob): the block about to be handed out, all `cls` bytes of it, is filled with the byte.
+  // Allocations happen while a run's persistent round tail is resident and while prefetch compares run on a second stream, so the
+  // fill neither synchronises the device nor touches the null stream: it goes out on a non-blocking stream of the cache's own, one
+  // per device, and only that stream is waited for, within the library's bound on device waits (a fill that never ends is
+  // hipErrorNotReady to the caller, not a hang).  Nothing is filled on release: work queued on the block may still be running.
+  // The streams live only while the knob is set: the first allocation that finds it unset again destroys them (once no fill is
+  // in flight), so a process that has used the knob is left with the streams - and the runtime's hardware queues - it had before.
+  hipError_t dev_poison(int dev, void *p, size_t cls) {
+    const int v = knobs().alloc_poison;
+    if (v < 0) {
+      if (fill_live_.load(std::memory_order_acquire)) {
+        std::lock_guard<std::mutex> g(mu_);
+        if (fill_users_ == 0) {
+          for (auto &f : fill_stream_) (void)hipStreamDestroy(f.second);   // (idle: every fill was waited for)
+          fill_stream_.clear();
+          fill_live_.store(false, std::memory_order_release);
+        }
+      }
+      return hipSuccess;
+    }
+    hipStream_t st = nullptr;
+    {
+      std::lock_guard<std::mutex> g(mu_);
+      auto it = fill_stream_.find(dev);
+      if (it == fill_stream_.end()) {
+        hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+        if (e != hipSuccess) return e;
+        fill_stream_[dev] = st;
+        fill_live_.store(true, std::memory_order_release);
+      } else st = it->second;
+      fill_users_++;
+    }
+    hipError_t e = hipMemsetAsync(p, v, cls, st);
+    if (e == hipSuccess) {
+      const auto t0 = std::chrono::steady_clock::now();
+      for (unsigned spins = 0; (e = hipStreamQuery(st)) == hipErrorNotReady; spins++) {
+        if (spins < 4096) continue;
+        std::this_thread::yield();
+        if ((spins & 0xFF) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > knobs().wait_timeout_s)
+          break;                                                           // (still hipErrorNotReady: the caller's time-out)
+      }
+    }
+    {
+      std::lock_guard<std::mutex> g(mu_);
+      fill_users_--;
+    }
+    if (e != hipSuccess) return e;
+    poison_[0].fetch_add(1, std::memory_order_relaxed);
+    poison_[1].fetch_add((int64_t)cls, std::memory_order_relaxed);
+    return hipSuccess;
+  }
+  std::map<int, hipStream_t> fill_stream_;
+  int fill_users_ = 0;                  // fills in flight on them (under mu_)
+  std::atomic<bool> fill_live_{false};  // fill_stream_ is not empty
+  std::atomic<int64_t> poison_[4]{};
   // cached device bytes are capped at a third of the device's memory (DADA2HIP_ALLOC_CACHE_GB overrides)
   size_t dev_cap() {
     if (cap_ == 0) {

@@ -65,6 +65,7 @@ struct Knobs {
   int ad_fast = 1;                    // DADA2HIP_AD_FAST=0             batch compares on the full aligner only (no pointer-free first pass)
   long long nw_ring = 0;              // DADA2HIP_NW_RING=n             waves of the lane aligners' scratch ring (a multiple of 4, at least 4; at most, and unset, the automatic size; tests: a wave's second and third chunk in a reused slot)
   long long upload_chunk_rows = 0;    // DADA2HIP_UPLOAD_CHUNK_ROWS=n   test knob: rows per chunk of the boundary's upload (rounded up to a multiple of 512; unset: about 16 MB of quality bytes; tests: chunk borders on small samples)
+  int alloc_poison = -1;              // DADA2HIP_ALLOC_POISON=<0..255> test knob: every block the allocation cache hands out, fresh or recycled, device or pinned, is filled with that byte over its whole size class first (hostpar.h; unset: handed out as it lies; tests: kernels and host passes that rely on what a buffer held before)
   int ad_debug = 0;                   // DADA2HIP_AD_DEBUG             profiling build only (make prof): skips phases of k_nw_ad, results void
   bool bimera_times = false;          // DADA2HIP_BIMERA_TIMES=1        stderr: host / device split of a bimera call
   long long bimera_slots = 0;         // DADA2HIP_BIMERA_SLOTS=n        isBimeraDenovo: work slots per launch (at least one chunk of the aligner; at most, and unset, what a bimera call's launch holds; tests: a window in several launches at small sizes)
@@ -149,6 +150,7 @@ struct Knobs {
     auto P = [&](const char *n) -> long long { const char *e = S(n); return e ? std::max(1ll, std::atoll(e)) : 0ll; };   // a size: 0 = unset
     k.tax_chunk = P("DADA2HIP_TAX_CHUNK"); k.filter_piece = P("DADA2HIP_FILTER_PIECE"); k.filter_piece_bytes = P("DADA2HIP_FILTER_PIECE_BYTES");
     k.upload_chunk_rows = P("DADA2HIP_UPLOAD_CHUNK_ROWS");
+    if (const char *e = S("DADA2HIP_ALLOC_POISON")) k.alloc_poison = *e ? std::max(0, std::min(255, std::atoi(e))) : -1;
     k.nw_ring = P("DADA2HIP_NW_RING"); k.bimera_slots = P("DADA2HIP_BIMERA_SLOTS");
     k.primers_piece = P("DADA2HIP_PRIMERS_PIECE"); k.primers_piece_bytes = P("DADA2HIP_PRIMERS_PIECE_BYTES"); k.primers_tile = P("DADA2HIP_PRIMERS_TILE");
     k.readqc_piece = P("DADA2HIP_READQC_PIECE"); k.readqc_piece_bytes = P("DADA2HIP_READQC_PIECE_BYTES");

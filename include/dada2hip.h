@@ -54,6 +54,9 @@
  *                                      the automatic size: 4 096 waves, halved down to 64 while the pointers would pass 6 GiB)
  *   DADA2HIP_UPLOAD_CHUNK_ROWS=<n>     rows per chunk of the boundary's upload (rounded up to a multiple of 512; default: about 16 MB of
  *                                      quality bytes; tests: chunk borders on small samples)
+ *   DADA2HIP_ALLOC_POISON=<0..255>     test knob: every block the allocation cache hands out (device and pinned, fresh or recycled) is
+ *                                      first filled with that byte over its whole size class, on a stream of the cache's own (default:
+ *                                      unset, blocks are handed out as they lie; dada2hip_alloc_poison_stats counts the fills)
  *   DADA2HIP_WAIT=block, DADA2HIP_WAIT_TIMEOUT_S=<s>   sleep instead of spin while waiting; bound of every device wait
  *   DADA2HIP_HOST_THREADS=<n>, DADA2HIP_ALLOC_CACHE=0, DADA2HIP_ALLOC_CACHE_GB=<n>   marshalling pool, allocation cache
  *   DADA2HIP_DEREP_INFLATE=zlib        dada2hip_derep_fastq, dada2hip_filter_fastq: .gz files through zlib's streaming inflate even where libdeflate is installed
@@ -231,6 +234,10 @@ int dada2hip_run_multi(int32_t n_samples, const dada2hip_sample_input *samples, 
  * drop-in replacement: back-to-back dada_uniques calls do not pay hipMalloc / hipFree again); this hands every cached
  * block back to the runtime.  DADA2HIP_ALLOC_CACHE=0 disables the cache. */
 void dada2hip_trim_cache(void);
+
+/* Test hook.  What DADA2HIP_ALLOC_POISON has filled since the process started: out[0] device blocks, out[1] device bytes, out[2]
+ * pinned blocks, out[3] pinned bytes (all 0 while the knob has never been set: a test reads from it that its knob was live). */
+void dada2hip_alloc_poison_stats(int64_t out[4]);
 
 /* ---- resident form --------------------------------------------------------------------------- */
 int dada2hip_sample_create(int32_t nraw, const char *const *seqs, const int32_t *abundances,

@@ -59,6 +59,11 @@ def main(which, mode, names):
         sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
         import build as emu_build
         _lib.LIB_PATH = emu_build.build()
+    run_cases(mode, names)
+
+
+def run_cases(mode, names):
+    """The cases through whatever library dada2_amd._lib points at (main, and tests/poison_cases.py in a process that has chosen it)."""
     import regime_cases as R
     from helpers import P_RTOL, assert_results_equal, tperr1
     from dada2_amd import api
