@@ -137,6 +137,8 @@ EXPORTS = [
     "dada2hip_seqtab_samples", "dada2hip_seqtab_free",
     "dada2hip_merge_run", "dada2hip_merge_run_nsamples", "dada2hip_merge_run_nrow", "dada2hip_merge_run_column", "dada2hip_merge_run_sequences",
     "dada2hip_merge_run_free",
+    "dada2hip_derep_reads_resident", "dada2hip_filter_derep_fastq_resident", "dada2hip_filter_derep_fastq_paired_resident",
+    "dada2hip_derep_has_quals", "dada2hip_derep_qmax", "dada2hip_sample_rows",
 ]
 
 BIMERA_DENOVO_NSTATS = 16   # DADA2HIP_BIMERA_DENOVO_NSTATS
@@ -224,6 +226,13 @@ DEREP_NSTATS = 16   # DADA2HIP_DEREP_NSTATS
 # the int64 words of dada2hip_derep_reads' stats, in order; dada2hip_filter_derep_fastq's are FILTER_NSTATS words of the filter, then these
 DEREP_STATS = ("reads_in", "uniques", "table_capacity", "rebuilds", "collision_rounds", "pieces", "upload_bytes", "download_bytes", "upload_us",
                "kernel_device_us", "download_us", "finalise_us", "total_us")
+
+RESIDENT_NSTATS = 16   # DADA2HIP_RESIDENT_NSTATS
+# the int64 words of the _resident entries' resident_stats, in order (a pair: the forward sample's, then the reverse sample's)
+RESIDENT_STATS = ("download_bytes", "upload_bytes", "rows_us", "order_us", "kernel_device_us", "kmers_device_us", "mirror_device_us", "blocks",
+                  "uniques")
+SAMPLE_ROWS_NGEOM = 8   # DADA2HIP_SAMPLE_ROWS_NGEOM
+SAMPLE_ROWS_GEOM = ("n", "W2", "LQ", "maxlen", "minlen", "qmax")
 
 
 class CSampleInput(C.Structure):
@@ -445,6 +454,16 @@ def lib():
                                               C.POINTER(i64), vp, cp, C.c_size_t]
     L.dada2hip_filter_derep_fastq_paired.argtypes = [vp, cp, cp, cp, cp, C.POINTER(CFilterParams), C.POINTER(CFilterParams), ip, i64, i64, ip,
                                                      C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), vp, cp, C.c_size_t]
+    L.dada2hip_derep_reads_resident.argtypes = [i64, vp, vp, vp, i64, ip, ip, C.POINTER(vp), C.POINTER(vp), vp, vp, cp, C.c_size_t]
+    L.dada2hip_filter_derep_fastq_resident.argtypes = [vp, cp, cp, C.POINTER(CFilterParams), ip, i64, i64, ip, C.POINTER(vp), C.POINTER(vp),
+                                                       C.POINTER(i64), C.POINTER(i64), vp, vp, cp, C.c_size_t]
+    L.dada2hip_filter_derep_fastq_paired_resident.argtypes = [vp, cp, cp, cp, cp, C.POINTER(CFilterParams), C.POINTER(CFilterParams), ip, i64, i64,
+                                                              ip, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64),
+                                                              C.POINTER(i64), vp, vp, cp, C.c_size_t]
+    for name in ("dada2hip_derep_has_quals", "dada2hip_derep_qmax"):
+        getattr(L, name).argtypes = [vp]
+        getattr(L, name).restype = ip
+    L.dada2hip_sample_rows.argtypes = [vp, vp, vp, vp, vp, vp, cp, C.c_size_t]
     L.dada2hip_trim_cache.argtypes = []
     L.dada2hip_trim_cache.restype = None
     L.dada2hip_alloc_poison_stats.argtypes = [C.POINTER(C.c_int64)]

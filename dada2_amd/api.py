@@ -213,9 +213,10 @@ class NativeDerep:
         return self
 
     def qmax(self) -> int:
-        """``ceiling(max(derep$quals, na.rm=TRUE))`` (R/dada.R:290), over the library's matrix in place."""
-        q = np.ctypeslib.as_array(_lib.lib().dada2hip_derep_quals(self._h), (self.nuniques, self.maxlen))
-        return int(np.ceil(np.nanmax(q)))
+        """``ceiling(max(derep$quals, na.rm=TRUE))`` (R/dada.R:290): dada2hip_derep_qmax, over the library's matrix in place - or,
+        for an object without a matrix (dada2_amd.dereplicate.ResidentDerep), the word the device stored.  (In the library, not
+        ``np.nanmax``: the matrix's NA is R's NA_real_, a signalling NaN, which numpy's vectorised fmax does not always skip.)"""
+        return int(_lib.lib().dada2hip_derep_qmax(self._h))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -342,6 +343,21 @@ class Sample:
         self.nraw = nd.nuniques
         self.device = device
         return self
+
+    def rows(self) -> dict:
+        """dada2hip_sample_rows: the resident rows as they lie on the device, padding included - ``seq2`` (n, W2) uint32, ``len``,
+        ``reads``, ``qual`` (n, LQ) uint8 - and the geometry words (_lib.SAMPLE_ROWS_GEOM)."""
+        L = _lib.lib()
+        eb = C.create_string_buffer(_EB)
+        g = np.zeros(_lib.SAMPLE_ROWS_NGEOM, dtype=np.int32)
+        _lib.check(L.dada2hip_sample_rows(self._h, g.ctypes.data, None, None, None, None, eb, _EB), eb)
+        out = {k: int(g[i]) for i, k in enumerate(_lib.SAMPLE_ROWS_GEOM)}
+        n = out["n"]
+        out.update(seq2=np.zeros((n, out["W2"]), dtype=np.uint32), len=np.zeros(n, dtype=np.int32), reads=np.zeros(n, dtype=np.uint32),
+                   qual=np.zeros((n, out["LQ"]), dtype=np.uint8))
+        _lib.check(L.dada2hip_sample_rows(self._h, None, out["seq2"].ctypes.data, out["len"].ctypes.data, out["reads"].ctypes.data,
+                                          out["qual"].ctypes.data, eb, _EB), eb)
+        return out
 
     def set_priors(self, priors):
         eb = C.create_string_buffer(_EB)

@@ -12,6 +12,7 @@
 //   * the final order is a STABLE sort by decreasing abundance (R's order(), :98), ties keep the order above.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <condition_variable>
 #include <cstring>
@@ -37,7 +38,16 @@ struct dada2hip_derep {
   std::unique_ptr<double[]> quals;   // [nuniques][maxlen], NA past each unique's length (filled by the host pool: first touch in parallel)
   int32_t maxlen = 0;
   int64_t nreads = 0;
+  // an object made by a *_resident entry (d2_derep_from_rows_resident) has no matrix: its means were rounded on the device, into
+  // the sample that came with it, and never came down.  qmax is then ceiling(max(derep$quals)) as the device found it
+  bool has_quals = true;
+  int32_t qmax = 0;
 };
+
+// what every entry that needs the matrix says about an object without one
+static const char *const NO_QUALS_MSG =
+    "dada2hip: this derep object has no quality matrix (it came with its resident sample from a *_resident entry, whose qualities "
+    "stay on the device); dada2hip_derep_reads / dada2hip_filter_derep_fastq keep the matrix.";
 
 namespace {
 
@@ -571,10 +581,26 @@ const int32_t *dada2hip_derep_abundances(const dada2hip_derep *d) { return d ? d
 const double *dada2hip_derep_quals(const dada2hip_derep *d) { return d ? d->quals.get() : nullptr; }
 const int32_t *dada2hip_derep_map(const dada2hip_derep *d) { return d ? d->map.data() : nullptr; }
 void dada2hip_derep_free(dada2hip_derep *d) { delete d; }
+int32_t dada2hip_derep_has_quals(const dada2hip_derep *d) { return d && d->has_quals ? 1 : 0; }
+
+// ceiling(max(derep$quals, na.rm = TRUE)) (R/dada.R:290): the stored word of an object without a matrix, else from the matrix
+int32_t dada2hip_derep_qmax(const dada2hip_derep *d) {
+  if (!d) return 0;
+  if (!d->has_quals) return d->qmax;
+  const size_t n = d->seq_ptrs.size() * (size_t)d->maxlen;
+  const double *q = d->quals.get();
+  double mx = -1e300;
+  bool any = false;
+  for (size_t i = 0; i < n; i++)
+    if (q[i] == q[i]) { mx = any ? std::max(mx, q[i]) : q[i]; any = true; }     // (NA past a unique's length is a NaN)
+  return any ? (int32_t)std::ceil(mx) : 0;
+}
 
 int dada2hip_sample_from_derep(const dada2hip_derep *d, const uint8_t *priors, int32_t device, dada2hip_sample **out, char *errbuf,
                                size_t errlen) {
+  if (out) *out = nullptr;
   if (!d) { set_err(errbuf, errlen, "dada2hip: no derep object"); return DADA2HIP_ERR_INPUT; }
+  if (!d->has_quals) { set_err(errbuf, errlen, NO_QUALS_MSG); return DADA2HIP_ERR_INPUT; }
   return dada2hip_sample_create((int32_t)d->seq_ptrs.size(), d->seq_ptrs.data(), d->abund.data(), priors, d->quals.get(), d->maxlen, device,
                                 out, errbuf, errlen);
 }
@@ -604,6 +630,7 @@ int derep_combine_body(int32_t nsamples, const dada2hip_derep_view *in, dada2hip
   int32_t maxlen = 0;
   for (int32_t s = 0; s < nsamples; s++) {
     const dada2hip_derep_view &v = in[s];
+    if (v.nuniques > 0 && v.seqs && v.abundances && !v.quals) { set_err(errbuf, errlen, NO_QUALS_MSG); return DADA2HIP_ERR_INPUT; }
     if (v.nuniques < 0 || v.maxlen < 0 || v.nreads < 0 || (v.nuniques > 0 && (!v.seqs || !v.abundances || !v.quals)) || (v.nreads > 0 && !v.map)) {
       set_err(errbuf, errlen, ("dada2hip: derep object " + std::to_string(s + 1) + " is incomplete.").c_str());
       return DADA2HIP_ERR_INPUT;
@@ -1526,9 +1553,10 @@ void dada2hip_complexity_free(double *values) { free(values); }
 // verdicts of the chunk are known (d2_dd_feed).  filter_files_body and the entries above are not touched by any of it.
 #include "derep_dev_plain.h"
 
-extern "C" int d2_derep_from_rows(int64_t nuniq, const int64_t *off, const int32_t *len, const int64_t *count, const int64_t *first,
-                                  const uint8_t *bytes, const uint64_t *sums, int64_t nreads, const int32_t *ruid, int64_t chunk_reads,
-                                  int32_t qual_offset, int32_t min_char, dada2hip_derep **out, char *errbuf, size_t errlen) {
+// sums null: the object without a quality matrix; order_out (nuniq words, or null): output row -> device unique
+static int derep_from_rows_body(int64_t nuniq, const int64_t *off, const int32_t *len, const int64_t *count, const int64_t *first,
+                                const uint8_t *bytes, const uint64_t *sums, int64_t nreads, const int32_t *ruid, int64_t chunk_reads,
+                                int32_t qual_offset, int32_t min_char, int32_t *order_out, dada2hip_derep **out, char *errbuf, size_t errlen) {
   return filter_files_guarded(errbuf, errlen, [&]() -> int {
     if (!out) { set_err(errbuf, errlen, "dada2hip: bad arguments"); return DADA2HIP_ERR_INPUT; }
     *out = nullptr;
@@ -1546,13 +1574,14 @@ extern "C" int d2_derep_from_rows(int64_t nuniq, const int64_t *off, const int32
     std::vector<size_t> soff(U + 1, 0);
     for (size_t k = 0; k < U; k++) soff[k + 1] = soff[k] + (size_t)len[P.order[k]] + 1;
     d->seq_blob.reset(new char[soff[U]]);
-    d->quals.reset(new double[U * ml]);
+    d->has_quals = sums != nullptr;
+    if (sums) d->quals.reset(new double[U * ml]);
     const double na = na_real();
     d2::parallel_for(U, 256, [&](size_t k0, size_t k1) {
       for (size_t k = k0; k < k1; k++) {
         const int32_t u = P.order[k];
         d->abund[k] = (int32_t)count[u];
-        dd_quality_row(R, u, offset, P.maxlen, na, &d->quals[k * ml]);
+        if (sums) dd_quality_row(R, u, offset, P.maxlen, na, &d->quals[k * ml]);
         char *dst = d->seq_blob.get() + soff[k];
         memcpy(dst, bytes + off[u], (size_t)len[u]);
         dst[len[u]] = 0;
@@ -1563,21 +1592,41 @@ extern "C" int d2_derep_from_rows(int64_t nuniq, const int64_t *off, const int32
     d2::parallel_for((size_t)nreads, 65536, [&](size_t i0, size_t i1) {
       for (size_t i = i0; i < i1; i++) d->map[i] = dd_map_entry(ruid[i], P, DADA2HIP_NA_INTEGER);
     });
+    if (order_out) memcpy(order_out, P.order.data(), U * sizeof(int32_t));
     *out = d.release();
     return DADA2HIP_OK;
   });
 }
+
+extern "C" int d2_derep_from_rows(int64_t nuniq, const int64_t *off, const int32_t *len, const int64_t *count, const int64_t *first,
+                                  const uint8_t *bytes, const uint64_t *sums, int64_t nreads, const int32_t *ruid, int64_t chunk_reads,
+                                  int32_t qual_offset, int32_t min_char, dada2hip_derep **out, char *errbuf, size_t errlen) {
+  if (!sums) { set_err(errbuf, errlen, "dada2hip: bad arguments"); return DADA2HIP_ERR_INPUT; }
+  return derep_from_rows_body(nuniq, off, len, count, first, bytes, sums, nreads, ruid, chunk_reads, qual_offset, min_char, nullptr, out, errbuf,
+                              errlen);
+}
+
+// the object of a *_resident entry: no sums came down, so no matrix; order (nuniq words): output row -> device unique, what the
+// device needs to write the sample's rows in the object's order.  The largest ceil(mean) follows by d2_derep_set_qmax.
+extern "C" int d2_derep_from_rows_resident(int64_t nuniq, const int64_t *off, const int32_t *len, const int64_t *count, const int64_t *first,
+                                           const uint8_t *bytes, int64_t nreads, const int32_t *ruid, int64_t chunk_reads, int32_t *order,
+                                           dada2hip_derep **out, char *errbuf, size_t errlen) {
+  if (!order) { set_err(errbuf, errlen, "dada2hip: bad arguments"); return DADA2HIP_ERR_INPUT; }
+  return derep_from_rows_body(nuniq, off, len, count, first, bytes, nullptr, nreads, ruid, chunk_reads, 33, 255, order, out, errbuf, errlen);
+}
+extern "C" void d2_derep_set_qmax(dada2hip_derep *d, int32_t qmax) { if (d) d->qmax = qmax; }
 
 namespace {
 
 int filter_derep_files_body(dada2hip_filter *ctx, int nfile, const char *const *in, const char *const *out,
                             const dada2hip_filter_params *const *params, int32_t compress, int64_t chunk_reads, int64_t derep_chunk_reads,
                             int32_t derep_qual_offset, dada2hip_derep **const *derep, int64_t *reads_in, int64_t *reads_out, int64_t *stats,
-                            char *errbuf, size_t errlen) {
+                            char *errbuf, size_t errlen, dada2hip_sample **const *sample = nullptr, int64_t *resident_stats = nullptr) {
   FqCall call(reads_in, reads_out);
   for (int k = 0; k < nfile; k++) {
-    if (!derep[k]) { set_err(errbuf, errlen, "dada2hip: bad arguments"); return DADA2HIP_ERR_INPUT; }
+    if (!derep[k] || (sample && !sample[k])) { set_err(errbuf, errlen, "dada2hip: bad arguments"); return DADA2HIP_ERR_INPUT; }
     *derep[k] = nullptr;
+    if (sample) *sample[k] = nullptr;
   }
   const bool write = out[0] != nullptr;
   for (int k = 0; k < nfile; k++)
@@ -1632,9 +1681,16 @@ int filter_derep_files_body(dada2hip_filter *ctx, int nfile, const char *const *
   int64_t *dst = tot + DADA2HIP_FILTER_NSTATS;
   for (int k = 0; k < nfile && dd[k].p; k++) {
     int64_t ds[DADA2HIP_DEREP_NSTATS] = {0};
-    const int r = d2_dd_finish(dd[k].p, 1, derep[k], ds, errbuf, errlen);
+    // (the resident form: the sample's rows are written on the device from the dereplicator's own buffers, no sum comes down)
+    const int r = sample ? d2_dd_finish_resident(dd[k].p, 1, derep[k], sample[k], ds, resident_stats ? resident_stats + k * DADA2HIP_RESIDENT_NSTATS : nullptr,
+                                                 errbuf, errlen)
+                         : d2_dd_finish(dd[k].p, 1, derep[k], ds, errbuf, errlen);
     if (r != DADA2HIP_OK) {
-      for (int j = 0; j < nfile; j++) { dada2hip_derep_free(*derep[j]); *derep[j] = nullptr; if (write) (void)remove(out[j]); }
+      for (int j = 0; j < nfile; j++) {
+        dada2hip_derep_free(*derep[j]); *derep[j] = nullptr;
+        if (sample) { dada2hip_sample_free(*sample[j]); *sample[j] = nullptr; }
+        if (write) (void)remove(out[j]);
+      }
       return r;
     }
     for (int i = 0; i < DD_COUNT; i++)                          // the forward object's words; of the reverse one the bytes and the clocks add
@@ -1668,6 +1724,35 @@ int dada2hip_filter_derep_fastq_paired(dada2hip_filter *ctx, const char *in_f, c
   return filter_files_guarded(errbuf, errlen, [&] {
     return filter_derep_files_body(ctx, 2, in, out, params, compress, chunk_reads, derep_chunk_reads, derep_qual_offset, dp, reads_in, reads_out,
                                    stats, errbuf, errlen);
+  });
+}
+
+int dada2hip_filter_derep_fastq_resident(dada2hip_filter *ctx, const char *in, const char *out, const dada2hip_filter_params *params,
+                                         int32_t compress, int64_t chunk_reads, int64_t derep_chunk_reads, int32_t derep_qual_offset,
+                                         dada2hip_derep **derep, dada2hip_sample **sample, int64_t *reads_in, int64_t *reads_out, int64_t *stats,
+                                         int64_t *resident_stats, char *errbuf, size_t errlen) {
+  dada2hip_derep **const dp[1] = {derep};
+  dada2hip_sample **const sp[1] = {sample};
+  if (resident_stats) memset(resident_stats, 0, sizeof(int64_t) * DADA2HIP_RESIDENT_NSTATS);
+  return filter_files_guarded(errbuf, errlen, [&] {
+    return filter_derep_files_body(ctx, 1, &in, &out, &params, compress, chunk_reads, derep_chunk_reads, derep_qual_offset, dp, reads_in, reads_out,
+                                   stats, errbuf, errlen, sp, resident_stats);
+  });
+}
+
+int dada2hip_filter_derep_fastq_paired_resident(dada2hip_filter *ctx, const char *in_f, const char *in_r, const char *out_f, const char *out_r,
+                                                const dada2hip_filter_params *params_f, const dada2hip_filter_params *params_r, int32_t compress,
+                                                int64_t chunk_reads, int64_t derep_chunk_reads, int32_t derep_qual_offset, dada2hip_derep **derep_f,
+                                                dada2hip_derep **derep_r, dada2hip_sample **sample_f, dada2hip_sample **sample_r, int64_t *reads_in,
+                                                int64_t *reads_out, int64_t *stats, int64_t *resident_stats, char *errbuf, size_t errlen) {
+  const char *in[2] = {in_f, in_r}, *out[2] = {out_f, out_r};
+  const dada2hip_filter_params *params[2] = {params_f, params_r};
+  dada2hip_derep **const dp[2] = {derep_f, derep_r};
+  dada2hip_sample **const sp[2] = {sample_f, sample_r};
+  if (resident_stats) memset(resident_stats, 0, sizeof(int64_t) * 2 * DADA2HIP_RESIDENT_NSTATS);
+  return filter_files_guarded(errbuf, errlen, [&] {
+    return filter_derep_files_body(ctx, 2, in, out, params, compress, chunk_reads, derep_chunk_reads, derep_qual_offset, dp, reads_in, reads_out,
+                                   stats, errbuf, errlen, sp, resident_stats);
   });
 }
 

@@ -299,6 +299,150 @@ int d2_dd_finish(void *dd, int32_t allow_none, dada2hip_derep **out, int64_t *st
   return rc;
 }
 
+// ---- the resident form: the uniques become a resident sample where they lie ---------------------------------------------------------
+// What d2_dd_finish brings down at 9 bytes per base only so that d2_derep_from_rows can divide it into doubles and
+// dada2hip_sample_from_derep can round them into bytes and send them up again, stays on the device here: the small rows come
+// down (28 bytes per unique and the arena's letters, for the order, the strings and the map), the order goes up at 4 bytes per
+// unique, and k_dd_to_sample (derep_resident.inc.hip) writes the sample's rows - packed letters, rounded qualities, length,
+// count - from the arena and the sums, in that order, on the sample's stream; the k-mer records are built behind it and the
+// packed rows come down once into the sample's pinned mirror (result strings are decoded from it).  The derep object has no
+// quality matrix (derep.cpp).  The sample's input errors are raised behind the kernel, in sample_create's order and with its
+// texts; the k-mer build is launched only if every length fits, as there.  On such an error the call returns NEITHER object -
+// the host route would have made the derep object and failed at dada2hip_sample_from_derep.
+namespace {
+
+void dd_to_sample(DerepDev &D, dada2hip_sample *s, const std::vector<int32_t> &len, const std::vector<int64_t> &cnt, const std::vector<int32_t> &order,
+                  int64_t *rs, int32_t *ceil_max) {
+  const auto t0 = clk::now();
+  std::lock_guard<std::mutex> lock(D.mu);
+  const size_t U = order.size();
+  int maxlen = 0, minlen = INT32_MAX;
+  uint64_t total = 0;
+  for (size_t u = 0; u < U; u++) {
+    maxlen = std::max(maxlen, len[u]); minlen = std::min(minlen, len[u]);
+    total += (uint32_t)cnt[u];
+  }
+  sample_shell(s, (int32_t)U, maxlen, D.device);
+  SampleDev &S = s->D;
+  DevBuf<int32_t> d_order;
+  DevBuf<DrRecord> d_rec;
+  PinBuf<DrRecord> h_rec;
+  d_order.alloc(U); d_rec.alloc(1); h_rec.alloc(1);
+  const auto t_up = clk::now();
+  const DrRecord r0 = {0, 0, 0, INT32_MIN};
+  D2_HIP(hipMemcpy(d_order.p, order.data(), U * sizeof(int32_t), hipMemcpyHostToDevice));
+  D2_HIP(hipMemcpy(d_rec.p, &r0, sizeof r0, hipMemcpyHostToDevice));
+  rs[DR_BYTES_UP] += (int64_t)(U * sizeof(int32_t) + sizeof r0);
+  add_lap(rs[DR_US_ORDER], t_up);
+  Events<4> ev;
+  ev.create();
+  D2_HIP(hipMemsetAsync(S.prior, 0, U, s->stream));
+  D2_HIP(hipEventRecord(ev[0], s->stream));
+  const int blocks = knobs().dd_sample_blocks > 0 ? knobs().dd_sample_blocks : 4096;
+  rs[DR_BLOCKS] = launch_dd_to_sample(D.state(), d_order.p, (int)U, dd_offset(D.qual_offset, D.h_ctr.p->minq), S, d_rec.p, blocks, s->stream);
+  D2_HIP(hipEventRecord(ev[1], s->stream));
+  // (the k-mer kernel trusts a row's length: only for rows that fit, as in sample_create; the call is going to fail otherwise)
+  const bool fits = maxlen < SEQLEN && minlen > KMER_SIZE;
+  if (fits) launch_build_kmers_rows(S, 0, (int)U, s->stream);
+  D2_HIP(hipEventRecord(ev[2], s->stream));
+  D2_HIP(hipMemcpyAsync(s->h_seq2.p, S.seq2, U * (size_t)S.W2 * 4, hipMemcpyDeviceToHost, s->stream));
+  D2_HIP(hipMemcpyAsync(h_rec.p, d_rec.p, sizeof(DrRecord), hipMemcpyDeviceToHost, s->stream));
+  D2_HIP(hipEventRecord(ev[3], s->stream));
+  sync_checked(s->stream);
+  rs[DR_BYTES_DOWN] += (int64_t)(U * (size_t)S.W2 * 4 + sizeof(DrRecord));
+  add_elapsed(rs[DR_US_KERNEL], ev[0], ev[1]);
+  add_elapsed(rs[DR_US_KMERS], ev[1], ev[2]);
+  add_elapsed(rs[DR_US_MIRROR], ev[2], ev[3]);
+  const DrRecord R = *h_rec.p;
+  if (maxlen >= SEQLEN) throw InputError{"Input sequences exceed the maximum allowed string length."};
+  if (minlen <= KMER_SIZE) throw InputError{"Input sequences must all be longer than the kmer-size (5)."};
+  if (R.bad_base) throw InputError{"Invalid derep$uniques vector. Sequences must be made up only of A/C/G/T."};
+  if (R.bad_qual) throw InputError{"Invalid derep$quals matrix. Quality values must be positive integers."};
+  for (size_t r = 0; r < U; r++) {
+    s->h_len[r] = len[(size_t)order[r]];
+    s->h_reads[r] = (uint32_t)cnt[(size_t)order[r]];
+  }
+  S.minlen = minlen;
+  s->total_reads = total;
+  s->qmax = R.qmax;
+  s->ms_upload = ms_since(t0);
+  *ceil_max = R.ceil_max;
+}
+
+}  // namespace
+
+int d2_dd_finish_resident(void *dd, int32_t allow_none, dada2hip_derep **out, dada2hip_sample **sample, int64_t *stats, int64_t *resident_stats,
+                          char *errbuf, size_t errlen) {
+  const auto t_call = clk::now();
+  std::vector<int64_t> off, cnt, fst;
+  std::vector<int32_t> len, order;
+  std::vector<uint8_t> bytes;
+  int64_t rs[DADA2HIP_RESIDENT_NSTATS] = {0};
+  DerepDev *D = (DerepDev *)dd;
+  int rc = guarded(errbuf, errlen, [&] {
+    if (!D || !out || !sample || D->no_qual) throw InputError{"dada2hip: bad arguments"};
+    *out = nullptr; *sample = nullptr;
+    if (allow_none && D->next_idx == 0) return;
+    if (D->nuniq == 0) throw InputError{"Only zero-length sequences detected during dereplication."};
+    std::lock_guard<std::mutex> lock(D->mu);
+    select_device(D->device);
+    const size_t U = (size_t)D->nuniq, A = (size_t)D->used;
+    off.resize(U); cnt.resize(U); fst.resize(U); len.resize(U); bytes.resize(A);
+    D2_HIP(hipMemcpy(off.data(), D->u_off.p, U * 8, hipMemcpyDeviceToHost));
+    D2_HIP(hipMemcpy(cnt.data(), D->u_count.p, U * 8, hipMemcpyDeviceToHost));
+    D2_HIP(hipMemcpy(fst.data(), D->u_first.p, U * 8, hipMemcpyDeviceToHost));
+    D2_HIP(hipMemcpy(len.data(), D->u_len.p, U * 4, hipMemcpyDeviceToHost));
+    D2_HIP(hipMemcpy(bytes.data(), D->arena.p, A, hipMemcpyDeviceToHost));          // (the letters; the sums stay where they are)
+    D2_HIP(hipMemcpy(D->h_ctr.p, D->ctr.p, sizeof(DdCounters), hipMemcpyDeviceToHost));
+    rs[DR_BYTES_DOWN] += (int64_t)(U * 28 + A + sizeof(DdCounters));
+    add_lap(rs[DR_US_ROWS], t_call);
+  });
+  if (rc != DADA2HIP_OK || !D || (allow_none && D->next_idx == 0)) {
+    if (rc == DADA2HIP_OK && D && stats) memcpy(stats, D->st, sizeof D->st);
+    return rc;
+  }
+  const auto t_final = clk::now();
+  order.resize(off.size());
+  dada2hip_derep *d = nullptr;
+  rc = d2_derep_from_rows_resident((int64_t)off.size(), off.data(), len.data(), cnt.data(), fst.data(), bytes.data(), (int64_t)D->ruid.size(),
+                                   D->ruid.data(), D->chunk_reads, order.data(), &d, errbuf, errlen);
+  add_lap(rs[DR_US_ORDER], t_final);
+  if (rc != DADA2HIP_OK) return rc;
+  dada2hip_sample *s = new dada2hip_sample();
+  int32_t ceil_max = 0;
+  rc = guarded(errbuf, errlen, [&] { dd_to_sample(*D, s, len, cnt, order, rs, &ceil_max); });
+  if (rc != DADA2HIP_OK) { dada2hip_sample_free(s); dada2hip_derep_free(d); return rc; }
+  d2_derep_set_qmax(d, ceil_max);
+  *out = d; *sample = s;
+  add_lap(D->st[DD_US_FINAL], t_final);
+  rs[DR_UNIQUES] = D->nuniq;
+  D->st[DD_BYTES_UP] += rs[DR_BYTES_UP]; D->st[DD_BYTES_DOWN] += rs[DR_BYTES_DOWN]; D->st[DD_US_DOWN] += rs[DR_US_ROWS];
+  D->st[DD_IN] = D->next_idx; D->st[DD_UNIQUES] = D->nuniq; D->st[DD_CAPACITY] = (int64_t)D->cap;
+  if (stats) memcpy(stats, D->st, sizeof D->st);
+  if (resident_stats) memcpy(resident_stats, rs, sizeof rs);
+  return rc;
+}
+
+int dada2hip_derep_reads_resident(int64_t n, const char *seq, const char *qual, const int64_t *offsets, int64_t chunk_reads, int32_t qual_offset,
+                                  int32_t device, dada2hip_derep **out, dada2hip_sample **sample, int64_t *stats, int64_t *resident_stats,
+                                  char *errbuf, size_t errlen) {
+  const auto t_call = clk::now();
+  if (out) *out = nullptr;
+  if (sample) *sample = nullptr;
+  if (resident_stats) memset(resident_stats, 0, sizeof(int64_t) * DADA2HIP_RESIDENT_NSTATS);
+  void *dd = nullptr;
+  int rc = d2_dd_open(device, chunk_reads, qual_offset, &dd, errbuf, errlen);
+  std::unique_ptr<DerepDev> hold((DerepDev *)dd);                // (the table, the arena and the sums are freed when the call returns)
+  if (rc == DADA2HIP_OK) rc = d2_dd_feed(dd, n, seq, qual, offsets, nullptr, nullptr, errbuf, errlen);
+  int64_t st[DADA2HIP_DEREP_NSTATS] = {0};
+  if (rc == DADA2HIP_OK) rc = d2_dd_finish_resident(dd, 0, out, sample, st, resident_stats, errbuf, errlen);
+  if (rc == DADA2HIP_OK && stats) {
+    st[DD_US_TOTAL] = (int64_t)(ms_since(t_call) * 1e3);
+    memcpy(stats, st, sizeof st);
+  }
+  return rc;
+}
+
 int dada2hip_derep_reads(int64_t n, const char *seq, const char *qual, const int64_t *offsets, int64_t chunk_reads, int32_t qual_offset,
                          int32_t device, dada2hip_derep **out, int64_t *stats, char *errbuf, size_t errlen) {
   const auto t_call = clk::now();

@@ -31,6 +31,16 @@ D2_HIDDEN int d2_dd_finish(void *dd, int32_t allow_none, dada2hip_derep **out, i
 D2_HIDDEN int d2_derep_from_rows(int64_t nuniq, const int64_t *off, const int32_t *len, const int64_t *count, const int64_t *first,
                                  const uint8_t *bytes, const uint64_t *sums, int64_t nreads, const int32_t *ruid, int64_t chunk_reads,
                                  int32_t qual_offset, int32_t min_char, dada2hip_derep **out, char *errbuf, size_t errlen);
+// The resident form (derep_dev_host.h).  d2_dd_finish_resident: the small rows come back, never the sums; d2_derep_from_rows_resident
+// (derep.cpp) makes the object without a quality matrix and says the order (output row -> device unique); the sample's rows are
+// written on the device in that order and d2_derep_set_qmax stores the largest ceil(mean) the device found.  An input error of
+// the sample (a letter outside ACGT, a read of five bases, a mean that is no byte) fails the call with neither object.
+D2_HIDDEN int d2_dd_finish_resident(void *dd, int32_t allow_none, dada2hip_derep **out, dada2hip_sample **sample, int64_t *stats,
+                                    int64_t *resident_stats, char *errbuf, size_t errlen);
+D2_HIDDEN int d2_derep_from_rows_resident(int64_t nuniq, const int64_t *off, const int32_t *len, const int64_t *count, const int64_t *first,
+                                          const uint8_t *bytes, int64_t nreads, const int32_t *ruid, int64_t chunk_reads, int32_t *order,
+                                          dada2hip_derep **out, char *errbuf, size_t errlen);
+D2_HIDDEN void d2_derep_set_qmax(dada2hip_derep *d, int32_t qmax);
 #undef D2_HIDDEN
 
 namespace {

@@ -556,6 +556,49 @@ void sample_create(dada2hip_sample *s, int32_t nraw, const char *const *seqs, co
   s->ms_upload = ms_since(t0);
 }
 
+// The shell of a resident sample of nraw rows of at most rowlen bases whose rows are written on the DEVICE (derep_dev_host.h,
+// d2_dd_finish_resident): the geometry, the streams and events and the buffers that sample_create lays out in front of its fused
+// pass, allocated beside it - sample_create itself, which bench.py times, is as it was.  Nothing is uploaded and nothing but
+// nw_flag is written: the caller fills seq2, len, reads, prior and qual on the sample's stream, builds the k-mer records behind
+// them, and sets D.minlen, the host vectors, total_reads and qmax.
+void sample_shell(dada2hip_sample *s, int32_t nraw, int rowlen, int device) {
+  select_device(device);
+  s->device = device;
+  D2_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+  D2_HIP(hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking));
+  D2_HIP(hipEventCreate(&s->ev0));
+  D2_HIP(hipEventCreate(&s->ev1));
+  SampleDev &D = s->D;
+  D.N = nraw; D.maxlen = rowlen; D.minlen = rowlen;
+  D.r_lo = 0; D.r_hi = nraw;
+  D.W2 = (((rowlen + 15) / 16) + 3) & ~3;
+  D.LQ = (rowlen + 15) & ~15;
+  D.LK = (std::max(rowlen - KMER_SIZE + 1, 1) + 7) & ~7;
+  D.HMAX = std::max(0, (rowlen - KMER_SIZE + 1) / (RANK_SAT + 1));
+  s->h_len.resize(nraw); s->h_reads.resize(nraw); s->h_prior.assign(nraw, 0);
+  s->h_seq2.alloc((size_t)nraw * D.W2);
+  s->seq2.alloc((size_t)nraw * D.W2);
+  s->nwflag.alloc(1);
+  D.nw_flag = s->nwflag.p;
+  D.ad_wpw = 64 * ((2 * rowlen + 1 + 15) / 16);                 // (k_nw_ad's pointer ring: its geometry only, as in sample_create)
+  int waves = 8192;
+  while (waves > 1024 && (size_t)waves * D.ad_wpw * 4 > ((size_t)256 << 20)) waves /= 2;
+  D.ad_ptr = nullptr;
+  D.ad_waves = waves;
+  D2_HIP(hipMemsetAsync(D.nw_flag, 0, 4, s->stream));
+  s->len.alloc(nraw); s->reads.alloc(nraw); s->prior.alloc(nraw); s->nheavy.alloc(nraw);
+  s->qual.alloc((size_t)nraw * D.LQ);
+  D.seq2 = s->seq2.p; D.len = s->len.p; D.reads = s->reads.p; D.prior = s->prior.p; D.nheavy = s->nheavy.p;
+  D.qual = s->qual.p;
+  s->kord.alloc((size_t)nraw * D.LK);
+  s->heavy.alloc((size_t)nraw * std::max(D.HMAX, 1));
+  D.kord = s->kord.p; D.heavy = s->heavy.p;
+  if (rowlen - KMER_SIZE + 1 <= 512 && knobs().screen_bits != 0) {
+    s->kbits.alloc((size_t)nraw * 32); s->kmult.alloc(nraw);
+    D.kbits = s->kbits.p; D.kmult = s->kmult.p;
+  } else { D.kbits = nullptr; D.kmult = nullptr; }
+}
+
 // a traceback that left its bounds (cannot happen with valid pointers; nwalign_endsfree.cpp:185 raises the same way)
 // the traceback-pointer ring of k_nw_ad for the time of one run (it comes from and goes back to the allocation cache)
 void ensure_ad_ring(dada2hip_sample *s) {
@@ -3131,6 +3174,27 @@ void dada2hip_sample_free(dada2hip_sample *s) {
 
 int32_t dada2hip_sample_nraw(const dada2hip_sample *s) { return s ? s->D.N : 0; }
 int32_t dada2hip_sample_maxlen(const dada2hip_sample *s) { return s ? s->D.maxlen : 0; }
+
+// the resident rows as they lie on the device, padding included (the tests compare two routes to a sample byte for byte)
+int dada2hip_sample_rows(dada2hip_sample *s, int32_t *geometry, uint32_t *seq2, int32_t *len, uint32_t *reads, uint8_t *qual, char *errbuf,
+                         size_t errlen) {
+  return guarded(errbuf, errlen, [&] {
+    if (!s) throw InputError{"dada2hip: bad arguments"};
+    const SampleDev &D = s->D;
+    if (geometry) {
+      const int32_t g[DADA2HIP_SAMPLE_ROWS_NGEOM] = {D.N, D.W2, D.LQ, D.maxlen, D.minlen, (int32_t)s->qmax, 0, 0};
+      memcpy(geometry, g, sizeof g);
+    }
+    if (!seq2 && !len && !reads && !qual) return;
+    select_device(s->device);
+    sync_spin(s->stream);
+    const size_t N = (size_t)D.N;
+    if (seq2) D2_HIP(hipMemcpy(seq2, D.seq2, N * D.W2 * 4, hipMemcpyDeviceToHost));
+    if (len) D2_HIP(hipMemcpy(len, D.len, N * 4, hipMemcpyDeviceToHost));
+    if (reads) D2_HIP(hipMemcpy(reads, D.reads, N * 4, hipMemcpyDeviceToHost));
+    if (qual) D2_HIP(hipMemcpy(qual, D.qual, N * D.LQ, hipMemcpyDeviceToHost));
+  });
+}
 
 int dada2hip_sample_run(dada2hip_sample *s, const double *err, int32_t err_ncol, const dada2hip_opts *opts,
                         const dada2hip_hooks *hooks, dada2hip_result **out, char *errbuf, size_t errlen) {

@@ -788,6 +788,12 @@ void launch_dd_hash(const DdState &T, const DdPiece &P, hipStream_t st);
 void launch_dd_round(const DdState &T, const DdPiece &P, hipStream_t st);   // claim, verify, publish, settle
 void launch_dd_rebuild(const DdState &T, int nuniq, hipStream_t st);
 // A piece with a null `qual` (and a state with null `sums`) is dereplicated without qualities: no smallest character, no sums.
+// The uniques into a resident sample's rows (derep_resident.inc.hip): row r of S from device unique order[r], the sums less
+// count x offset rounded on integers.  DrRecord, zeroed but for ceil_max = INT32_MIN: a letter outside ACGT, a mean that rounds
+// into no byte, the largest byte, the largest ceil(mean).  blocks caps the grid; the blocks launched come back.
+struct DrRecord { int32_t bad_base, bad_qual, qmax, ceil_max; };
+int launch_dd_to_sample(const DdState &T, const int32_t *d_order, int nuniq, int offset, const SampleDev &S, DrRecord *d_rec, int blocks,
+                        hipStream_t st);
 // mergeSequenceTables on the dereplicator's state (seqtab.inc.hip): the column names of all tables are its "reads".  ST_ERR_*: the
 // error word of StCounters; bad_first: the smallest first appearance (running column number) of a unique with a letter that has no
 // complement; rc_fails: lookups of a reverse complement that met its hash, compared bytes and found them different.

@@ -3008,6 +3008,7 @@ void launch_bimera_lr(const SampleDev &S, const int32_t *d_chunk_centre, const i
 #include "primers.inc.hip"   // removePrimers: the bit planes of a read, the four-pattern search with a bit-sliced mismatch counter, the verdict
 #include "readqc.inc.hip"    // read diagnostics: the per-cycle quality table; the windowed k-mer complexity of a read
 #include "derep_dev.inc.hip" // the device dereplicator: hash, claim, verify, publish, settle; the table's rebuild
+#include "derep_resident.inc.hip" // ... its uniques into a resident sample's rows: packed letters, rounded qualities, the tallies
 #include "seqtab.inc.hip"    // mergeSequenceTables: the reverse complement's lookup in the dereplicator's table, accumulate, column keys, gather
 #include "merge.inc.hip"     // mergePairs over a run: the pair table of a sample, C_eval_pair and C_pair_consensus on the aligner's move strings
 #include "priors.inc.hip"    // priors by sequence: a lane per resident unique, its prefix key searched among the prior sequences' keys

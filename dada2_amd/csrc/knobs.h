@@ -85,6 +85,7 @@ struct Knobs {
   long long derep_piece_bytes = 0;    // DADA2HIP_DEREP_PIECE_BYTES=n   ... bases per piece (at least 1; at most, and unset, 32 MiB; a longer read is a piece of its own)
   long long derep_table = 0;          // DADA2HIP_DEREP_TABLE=n         ... slots of the table at the start (rounded up to a power of two, at least 8; unset: 131 072; tests: the rebuild)
   int derep_hash_bits = 64;           // DADA2HIP_DEREP_HASH_BITS=k     ... the hash masked to k bits (0..64; tests: true collisions, 0 = every read with every other)
+  int dd_sample_blocks = 0;           // DADA2HIP_DD_SAMPLE_BLOCKS=n    ... block cap of k_dd_to_sample, the uniques into a resident sample's rows (0 = 4 096; tests: waves that stride on a few hundred uniques)
   int merge_hash_bits = 64;           // DADA2HIP_MERGE_HASH_BITS=k     run-level mergePairs: the pair table's hash masked to k bits (0..64; tests: true collisions, 0 = every pair walks from slot 0)
   long long merge_chunk = 0;          // DADA2HIP_MERGE_CHUNK=n         ... unique pairs per chunk of the aligner (at least 1; at most, and unset, 65 536; tests: chunk borders inside and between samples)
   int species_cand = 1 << 20;         // DADA2HIP_SPECIES_CAND=n       assignSpecies: records of the candidate buffer and of the hit buffer (a launch that counts more is re-run in pieces)
@@ -156,6 +157,7 @@ struct Knobs {
     k.readqc_piece = P("DADA2HIP_READQC_PIECE"); k.readqc_piece_bytes = P("DADA2HIP_READQC_PIECE_BYTES");
     k.derep_piece = P("DADA2HIP_DEREP_PIECE"); k.derep_piece_bytes = P("DADA2HIP_DEREP_PIECE_BYTES"); k.derep_table = P("DADA2HIP_DEREP_TABLE");
     k.derep_hash_bits = std::max(0, std::min(64, I("DADA2HIP_DEREP_HASH_BITS", 64)));
+    k.dd_sample_blocks = std::max(0, I("DADA2HIP_DD_SAMPLE_BLOCKS", 0));
     k.merge_hash_bits = std::max(0, std::min(64, I("DADA2HIP_MERGE_HASH_BITS", 64))); k.merge_chunk = P("DADA2HIP_MERGE_CHUNK");
     k.species_cand = I("DADA2HIP_SPECIES_CAND", 1 << 20); k.species_chunk = I("DADA2HIP_SPECIES_CHUNK", 8192);
     k.priors_lds_keys = I("DADA2HIP_PRIORS_LDS_KEYS", 4096); k.priors_grid = I("DADA2HIP_PRIORS_GRID", 0);

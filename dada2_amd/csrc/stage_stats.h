@@ -35,6 +35,9 @@ enum { RQ_CALL_FIRST = RQ_PIECES, RQ_CALL_LAST = RQ_US_DOWN };   // the words of
 enum { DD_IN = 0, DD_UNIQUES, DD_CAPACITY, DD_REBUILDS, DD_ROUNDS, DD_PIECES, DD_BYTES_UP, DD_BYTES_DOWN, DD_US_UP, DD_US_KERNEL, DD_US_DOWN,
        DD_US_FINAL, DD_US_TOTAL, DD_COUNT };
 static_assert(DD_COUNT <= DADA2HIP_DEREP_NSTATS, "stats words");
+// ... its resident form's own words (dada2hip_derep_reads_resident and the fused entries: resident_stats)
+enum { DR_BYTES_DOWN = 0, DR_BYTES_UP, DR_US_ROWS, DR_US_ORDER, DR_US_KERNEL, DR_US_KMERS, DR_US_MIRROR, DR_BLOCKS, DR_UNIQUES, DR_COUNT };
+static_assert(DR_COUNT <= DADA2HIP_RESIDENT_NSTATS, "stats words");
 // dada2hip_seqtab_merge
 enum { SM_TABLES = 0, SM_COLS_IN, SM_DISTINCT, SM_FLAGGED, SM_ROWS, SM_COLS, SM_CAPACITY, SM_REBUILDS, SM_ROUNDS, SM_RC_FAILS, SM_PIECES,
        SM_BYTES_UP, SM_BYTES_DOWN, SM_US_UP, SM_US_IDENTITY, SM_US_RC, SM_US_ACCUM, SM_US_DOWN, SM_US_TOTAL, SM_COUNT };

@@ -7,7 +7,14 @@ written, deflated, inflated or parsed a second time.  Both return ``api.NativeDe
 reads (of the filtered file) field for field.  ``dada2_amd.api`` neither imports nor re-exports this module.
 
 ``filter_and_derep`` takes ``api.filter_and_trim``'s arguments and gives its warnings; ``orient_fwd`` and ``match_ids`` are
-refused - they stay with ``dada2_amd.filtering``, unfused."""
+refused - they stay with ``dada2_amd.filtering``, unfused.
+
+The resident forms - ``derep_reads_resident``, ``filter_and_sample`` - end where ``dada()`` starts: they return ``ResidentDerep``
+objects, each with the resident ``Sample`` that ``Sample.from_native`` would have made of it.  The dereplicator's quality sums
+never leave the device: one kernel rounds them into the sample's quality bytes where they lie (byte for byte the rows of the
+host route).  A ``ResidentDerep`` therefore has no quality matrix - sequences, abundances, map and ``qmax()`` are all
+``dada()``, ``paired.merge_pairs`` and ``learn_errors`` read; ``to_derep``, ``Sample.from_native``, ``api.combine_dereps`` and
+``dada(pool=True)`` refuse it and say why.  ``dada`` here is ``api.dada`` on the samples the dereps came with."""
 from __future__ import annotations
 
 import ctypes as C
@@ -21,6 +28,41 @@ from . import _lib, api
 _EB = 2048
 STATS = _lib.DEREP_STATS                                  # the int64 words of dada2hip_derep_reads' stats
 FUSED_STATS = _lib.FILTER_STATS + ("",) * (_lib.FILTER_NSTATS - len(_lib.FILTER_STATS)) + tuple("derep_" + k for k in STATS)
+RESIDENT_STATS = _lib.RESIDENT_STATS                     # the int64 words of the resident entries' resident_stats
+NO_MATRIX = ("a ResidentDerep has no quality matrix: its qualities were rounded on the device, into the sample it came with "
+             "(.sample); filter_and_derep / derep_reads are the routes that keep the matrix.")
+
+
+class ResidentDerep(api.NativeDerep):
+    """The derep object of a resident entry: an ``api.NativeDerep`` without a quality matrix, and ``.sample``, the resident
+    ``api.Sample`` of its uniques (rows byte for byte those of ``Sample.from_native`` on the full object).  ``qmax()`` is the
+    word the device stored: the largest ``ceil(mean)`` it met while rounding."""
+
+    def __init__(self, *a, **k):
+        raise TypeError("ResidentDerep objects come from derep_reads_resident and filter_and_sample.")
+
+    @classmethod
+    def _from_handles(cls, h, hs, device):
+        self = cls._from_handle(h)
+        smp = api.Sample.__new__(api.Sample)
+        smp._h, smp.nraw, smp.device = hs, self.nuniques, device
+        self.sample = smp
+        return self
+
+    def to_derep(self):
+        raise ValueError(NO_MATRIX)
+
+    def close(self):
+        smp = getattr(self, "sample", None)
+        if smp is not None:
+            smp.close()
+        super().close()
+
+
+def _resident_stats_out(stats, rs, prefixes):
+    if stats is not None:
+        for j, pre in enumerate(prefixes):
+            stats.update({pre + k: int(rs[j * _lib.RESIDENT_NSTATS + i]) for i, k in enumerate(RESIDENT_STATS)})
 
 
 def _bytes(strs):
@@ -47,12 +89,32 @@ def derep_reads(seqs, quals, n: int = 10**6, qual_offset: int = 0, device: int =
     return api.NativeDerep._from_handle(h)
 
 
+def derep_reads_resident(seqs, quals, n: int = 10**6, qual_offset: int = 0, device: int = 0, stats: dict = None) -> ResidentDerep:
+    """dada2hip_derep_reads_resident: ``derep_reads``' arguments -> ResidentDerep (with ``.sample``).  ``stats`` gets
+    ``derep_reads``' words and, as ``resident_<word>``, RESIDENT_STATS.  An input error of the sample (a letter outside A/C/G/T, a
+    read of at most five bases, a mean quality that is no byte) fails the call - there is no derep object to look at."""
+    sb, off = _bytes(seqs)
+    qb, qoff = _bytes(quals)
+    if not np.array_equal(off, qoff):
+        raise ValueError("Every read needs as many quality characters as bases.")
+    h, hs = C.c_void_p(), C.c_void_p()
+    st = np.zeros(_lib.DEREP_NSTATS, dtype=np.int64)
+    rs = np.zeros(_lib.RESIDENT_NSTATS, dtype=np.int64)
+    eb = C.create_string_buffer(_EB)
+    _lib.check(_lib.lib().dada2hip_derep_reads_resident(len(off) - 1, sb, qb, off.ctypes.data, int(n), int(qual_offset), int(device), C.byref(h),
+                                                        C.byref(hs), st.ctypes.data, rs.ctypes.data, eb, _EB), eb)
+    if stats is not None:
+        stats.update({k: int(st[i]) for i, k in enumerate(STATS)})
+    _resident_stats_out(stats, rs, ("resident_",))
+    return ResidentDerep._from_handles(h, hs, int(device))
+
+
 def _stats_out(stats, st):
     if stats is not None:
         stats.update({k: int(st[i]) for i, k in enumerate(FUSED_STATS) if k})
 
 
-def _fused_single(found, n_derep, derep_qual_offset):
+def _fused_single(found, n_derep, derep_qual_offset, resident=False):
     def run(fn, fout, *, compress=True, n=10**6, quality_type=0, verbose=False, rm_phix=False, ctx=None, device=0, stats=None,
             min_matches=2, non_overlapping=True, kmer_size=0, **kw):
         for k, v in kw.items():
@@ -64,24 +126,36 @@ def _fused_single(found, n_derep, derep_qual_offset):
         try:
             p = api.filter_params(rm_phix=bool(rm_phix), min_matches=min_matches, non_overlapping=non_overlapping, kmer_size=kmer_size,
                                   quality_type=quality_type, **kw)
-            rin, rout, h = C.c_int64(), C.c_int64(), C.c_void_p()
+            rin, rout, h, hs = C.c_int64(), C.c_int64(), C.c_void_p(), C.c_void_p()
             st = np.zeros(_lib.FILTER_NSTATS + _lib.DEREP_NSTATS, dtype=np.int64)
+            rs = np.zeros(_lib.RESIDENT_NSTATS, dtype=np.int64)
             eb = C.create_string_buffer(_EB)
-            _lib.check(_lib.lib().dada2hip_filter_derep_fastq(c._h, os.fspath(fn).encode(), None if fout is None else os.fspath(fout).encode(),
-                                                              C.byref(p), int(bool(compress)), int(n), int(n_derep), int(derep_qual_offset),
-                                                              C.byref(h), C.byref(rin), C.byref(rout), st.ctypes.data, eb, _EB), eb)
+            fin, fo = os.fspath(fn).encode(), None if fout is None else os.fspath(fout).encode()
+            if resident:
+                _lib.check(_lib.lib().dada2hip_filter_derep_fastq_resident(c._h, fin, fo, C.byref(p), int(bool(compress)), int(n), int(n_derep),
+                                                                           int(derep_qual_offset), C.byref(h), C.byref(hs), C.byref(rin),
+                                                                           C.byref(rout), st.ctypes.data, rs.ctypes.data, eb, _EB), eb)
+            else:
+                _lib.check(_lib.lib().dada2hip_filter_derep_fastq(c._h, fin, fo, C.byref(p), int(bool(compress)), int(n), int(n_derep),
+                                                                  int(derep_qual_offset), C.byref(h), C.byref(rin), C.byref(rout), st.ctypes.data,
+                                                                  eb, _EB), eb)
+            dev = c.device
         finally:
             if own:
                 c.close()
         _stats_out(stats, st)
-        found.append(api.NativeDerep._from_handle(h) if h else None)
+        if resident:
+            _resident_stats_out(stats, rs, ("resident_",))
+            found.append(ResidentDerep._from_handles(h, hs, dev) if h else None)
+        else:
+            found.append(api.NativeDerep._from_handle(h) if h else None)
         if verbose:
             print(f"Read in {rin.value}, output {rout.value} ({round(rout.value * 100 / max(rin.value, 1), 1)}%) filtered sequences.")
         return rin.value, rout.value
     return run
 
 
-def _fused_pair(found, n_derep, derep_qual_offset):
+def _fused_pair(found, n_derep, derep_qual_offset, resident=False):
     def run(fn, fout, *, compress=True, n=10**6, quality_type=0, verbose=False, rm_phix=False, ctx=None, device=0, stats=None,
             min_matches=2, non_overlapping=True, kmer_size=0, **kw):
         if isinstance(fn, str) or len(fn) != 2:
@@ -95,19 +169,31 @@ def _fused_pair(found, n_derep, derep_qual_offset):
         try:
             ps = [api.filter_params(w, rm_phix=bool(rm_phix), min_matches=min_matches, non_overlapping=non_overlapping, kmer_size=kmer_size,
                                     quality_type=quality_type, **kw) for w in (0, 1)]
-            rin, rout, hf, hr = C.c_int64(), C.c_int64(), C.c_void_p(), C.c_void_p()
+            rin, rout, hf, hr, sf, sr = C.c_int64(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
             st = np.zeros(_lib.FILTER_NSTATS + _lib.DEREP_NSTATS, dtype=np.int64)
+            rs = np.zeros(2 * _lib.RESIDENT_NSTATS, dtype=np.int64)
             eb = C.create_string_buffer(_EB)
             outs = (None, None) if fout is None else tuple(os.fspath(f).encode() for f in fout)
-            _lib.check(_lib.lib().dada2hip_filter_derep_fastq_paired(c._h, os.fspath(fn[0]).encode(), os.fspath(fn[1]).encode(), outs[0], outs[1],
-                                                                     C.byref(ps[0]), C.byref(ps[1]), int(bool(compress)), int(n), int(n_derep),
-                                                                     int(derep_qual_offset), C.byref(hf), C.byref(hr), C.byref(rin),
-                                                                     C.byref(rout), st.ctypes.data, eb, _EB), eb)
+            if resident:
+                _lib.check(_lib.lib().dada2hip_filter_derep_fastq_paired_resident(
+                    c._h, os.fspath(fn[0]).encode(), os.fspath(fn[1]).encode(), outs[0], outs[1], C.byref(ps[0]), C.byref(ps[1]), int(bool(compress)),
+                    int(n), int(n_derep), int(derep_qual_offset), C.byref(hf), C.byref(hr), C.byref(sf), C.byref(sr), C.byref(rin), C.byref(rout),
+                    st.ctypes.data, rs.ctypes.data, eb, _EB), eb)
+            else:
+                _lib.check(_lib.lib().dada2hip_filter_derep_fastq_paired(c._h, os.fspath(fn[0]).encode(), os.fspath(fn[1]).encode(), outs[0], outs[1],
+                                                                         C.byref(ps[0]), C.byref(ps[1]), int(bool(compress)), int(n), int(n_derep),
+                                                                         int(derep_qual_offset), C.byref(hf), C.byref(hr), C.byref(rin),
+                                                                         C.byref(rout), st.ctypes.data, eb, _EB), eb)
+            dev = c.device
         finally:
             if own:
                 c.close()
         _stats_out(stats, st)
-        found.append((api.NativeDerep._from_handle(hf), api.NativeDerep._from_handle(hr)) if hf and hr else None)
+        if resident:
+            _resident_stats_out(stats, rs, ("resident_", "resident_rev_"))
+            found.append((ResidentDerep._from_handles(hf, sf, dev), ResidentDerep._from_handles(hr, sr, dev)) if hf and hr else None)
+        else:
+            found.append((api.NativeDerep._from_handle(hf), api.NativeDerep._from_handle(hr)) if hf and hr else None)
         if verbose:
             print(f"Read in {rin.value} paired-sequences, output {rout.value} ({round(rout.value * 100 / max(rin.value, 1), 1)}%) filtered paired-sequences.")
         return rin.value, rout.value
@@ -121,19 +207,33 @@ def filter_and_derep(fwd, filt=None, rev=None, filt_rev=None, *, n_derep: int = 
     filtered file is written; otherwise the files are api.filter_and_trim's byte for byte.  The derep objects are what
     api.derep_fastq(filt, n_derep, derep_qual_offset) gives for those files.  None when no read passes (with filterAndTrim's warning).
     ``filter_args``: api.filter_and_trim's (trunc_len, max_ee, ..., n, compress, rm_phix, ctx, device, verbose)."""
+    return _filter_and("filter_and_derep", False, fwd, filt, rev, filt_rev, n_derep, derep_qual_offset, stats, filter_args)
+
+
+def filter_and_sample(fwd, filt=None, rev=None, filt_rev=None, *, n_derep: int = 10**6, derep_qual_offset: int = 0, stats: dict = None,
+                      **filter_args):
+    """``filter_and_derep`` with the resident end: ``(counts, ResidentDerep | None)``, for a pair ``(counts, (ResidentDerepF,
+    ResidentDerepR) | None)`` - every object with its resident ``.sample``, ready for ``dada``.  The arguments, the refusals, the
+    files written and the warning are ``filter_and_derep``'s; ``stats`` also gets RESIDENT_STATS as ``resident_<word>`` (the reverse
+    sample's as ``resident_rev_<word>``).  An input error of a sample (an N that ``max_n`` let through, a read of at most five bases)
+    fails the call and leaves no file."""
+    return _filter_and("filter_and_sample", True, fwd, filt, rev, filt_rev, n_derep, derep_qual_offset, stats, filter_args)
+
+
+def _filter_and(name, resident, fwd, filt, rev, filt_rev, n_derep, derep_qual_offset, stats, filter_args):
     for k in ("orient_fwd", "match_ids"):
         v = filter_args.get(k)
         if v is not None and v is not False:
-            raise NotImplementedError(f"{k} is not supported by filter_and_derep: filter with dada2_amd.filtering, then dereplicate the file.")
+            raise NotImplementedError(f"{k} is not supported by {name}: filter with dada2_amd.filtering, then dereplicate the file.")
     if not (isinstance(fwd, (str, bytes)) or hasattr(fwd, "__fspath__")):
-        raise ValueError("filter_and_derep takes one sample: one forward file (and one reverse file).")
+        raise ValueError(f"{name} takes one sample: one forward file (and one reverse file).")
     if rev is not None and not (isinstance(rev, (str, bytes)) or hasattr(rev, "__fspath__")):
-        raise ValueError("filter_and_derep takes one sample: one forward file (and one reverse file).")
+        raise ValueError(f"{name} takes one sample: one forward file (and one reverse file).")
     paired = rev is not None
     if paired and (filt is None) != (filt_rev is None):
         raise ValueError("Output files for both directions, or for neither.")
     found = []
-    per_file = (_fused_single(found, n_derep, derep_qual_offset), _fused_pair(found, n_derep, derep_qual_offset))
+    per_file = (_fused_single(found, n_derep, derep_qual_offset, resident), _fused_pair(found, n_derep, derep_qual_offset, resident))
     if filt is not None:
         args = dict(filter_args)
         st = {}
@@ -157,3 +257,20 @@ def filter_and_derep(fwd, filt=None, rev=None, filt_rev=None, *, n_derep: int = 
     if rout == 0:
         warnings.warn("No reads passed the filter. Please revisit your filtering parameters.")
     return (rin, rout), found[0]
+
+
+def dada(dereps, err, **kw):
+    """``api.dada(dereps, err, samples=[d.sample ...], **kw)`` for ``ResidentDerep`` objects: the samples they came with are run as
+    they lie (and stay open - they are the dereps').  ``pool="pseudo"`` works, the samples stay separate; ``pool=True`` needs the
+    combined quality matrix and is refused with the combine's message."""
+    single = isinstance(dereps, api.NativeDerep)
+    ds = [dereps] if single else list(dereps)
+    if not ds or not all(isinstance(d, ResidentDerep) for d in ds):
+        raise ValueError("dereplicate.dada takes ResidentDerep objects (derep_reads_resident, filter_and_sample); api.dada takes the others.")
+    if "samples" in kw:
+        raise ValueError("dereplicate.dada runs the samples its dereps came with: samples= does not apply.")
+    pool = kw.get("pool", False)
+    if isinstance(pool, (bool, np.bool_)) and bool(pool) and len(ds) > 1:
+        api._combine_native(ds)[0].close()                          # (raises: the combine says what is missing)
+        raise ValueError(NO_MATRIX)
+    return api.dada(dereps, err, samples=[d.sample for d in ds], **kw)

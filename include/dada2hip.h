@@ -81,6 +81,8 @@
  *   DADA2HIP_DEREP_PIECE_BYTES=<n>     ... bases per piece (at least 1; default and at most 32 MiB; a longer read is a piece of its own)
  *   DADA2HIP_DEREP_TABLE=<n>           the device dereplicator: slots of its table at the start (a power of two from 8 on; default 131 072)
  *   DADA2HIP_DEREP_HASH_BITS=<k>       ... its hash masked to k bits (0..64; default 64; 0: every read collides with every other)
+ *   DADA2HIP_DD_SAMPLE_BLOCKS=<n>      dada2hip_derep_reads_resident and the fused _resident entries: block cap of the kernel that writes the
+ *                                      sample's rows (default 4 096; a small value makes its waves stride over the uniques)
  *   DADA2HIP_MERGE_HASH_BITS=<k>       dada2hip_merge_run: the pair table's hash masked to k bits (0..64; default 64; 0: every pair walks from slot 0)
  *   DADA2HIP_MERGE_CHUNK=<n>           ... unique pairs per chunk of the aligner (at least 1; default and at most 65 536)
  *   DADA2HIP_PRIORS_LDS_KEYS=<n>       dada2hip_sample_set_prior_seqs: up to n distinct prefix keys are searched in LDS, more in global
@@ -419,11 +421,17 @@ int64_t dada2hip_derep_nreads(const dada2hip_derep *d);
 int32_t dada2hip_derep_maxlen(const dada2hip_derep *d);
 const char *const *dada2hip_derep_seqs(const dada2hip_derep *d);
 const int32_t *dada2hip_derep_abundances(const dada2hip_derep *d);
-const double *dada2hip_derep_quals(const dada2hip_derep *d);
+const double *dada2hip_derep_quals(const dada2hip_derep *d);   /* NULL for an object without a matrix (dada2hip_derep_has_quals) */
 const int32_t *dada2hip_derep_map(const dada2hip_derep *d);
 void dada2hip_derep_free(dada2hip_derep *d);
 int dada2hip_sample_from_derep(const dada2hip_derep *d, const uint8_t *priors, int32_t device, dada2hip_sample **out,
                                char *errbuf, size_t errlen);
+/* An object from a _resident entry (below) has no quality matrix: dada2hip_derep_has_quals is 0, dada2hip_derep_quals is NULL,
+ * and dada2hip_sample_from_derep, dada2hip_derep_combine (for a view with quals == NULL) return DADA2HIP_ERR_INPUT with one
+ * message that says so.  dada2hip_derep_qmax is ceiling(max(derep$quals, na.rm = TRUE)) (R/dada.R:290) of either kind of object:
+ * from the matrix, or the word the device stored. */
+int32_t dada2hip_derep_has_quals(const dada2hip_derep *d);
+int32_t dada2hip_derep_qmax(const dada2hip_derep *d);
 
 /* ---- dereplication on the device: reads in memory, or the reads filterAndTrim keeps, to a derep object ------------------
  * dada2hip_derep_reads: n reads in the layout of dada2hip_filter_reads (read r is seq / qual[offsets[r] .. offsets[r + 1]))
@@ -446,6 +454,35 @@ int dada2hip_sample_from_derep(const dada2hip_derep *d, const uint8_t *priors, i
 #define DADA2HIP_DEREP_NSTATS 16
 int dada2hip_derep_reads(int64_t n, const char *seq, const char *qual, const int64_t *offsets, int64_t chunk_reads,
                          int32_t qual_offset, int32_t device, dada2hip_derep **out, int64_t *stats, char *errbuf, size_t errlen);
+
+/* ---- ... and straight to a resident sample ------------------------------------------------------------------------------
+ * dada2hip_derep_reads_resident takes dada2hip_derep_reads' arguments and returns the derep object AND the resident sample that
+ * dada2hip_sample_from_derep would make of it (no priors) - without the quality sums leaving the device.  At the end of the call
+ * the device holds the uniques' letters, a 64-bit sum per base and the counts: 28 bytes per unique and the letters come down
+ * (for the order, the strings, the abundances and the map), the order goes up at 4 bytes per unique, and one kernel writes the
+ * sample's rows where the data lies: the letters packed into 2-bit words, the sums less count x offset rounded to the byte
+ * that round(mean) gives (on integers: half away from zero, a mean that rounds below 0 or above 255 is the reference's
+ * "Quality values must be positive integers."), every pad word and byte zero.  The rows are byte for byte those of the host
+ * route; the k-mer records are built behind them and the packed rows come down once, into the sample's host mirror.
+ * *out is a derep object WITHOUT a quality matrix (above): sequences, abundances, map, maxlen, nreads and dada2hip_derep_qmax are
+ * those of dada2hip_derep_reads' object.  The sample is an ordinary one: dada2hip_sample_run, _set_priors, _set_prior_seqs, _free.
+ * Errors: dada2hip_derep_reads', and the input errors of dada2hip_sample_create with its texts and in its order (a read at or
+ * above the maximum length, a read of at most five bases, a letter outside A/C/G/T, a mean that is no byte).  On any error the
+ * call returns NEITHER object - dada2hip_derep_reads would have returned the derep object, and dada2hip_sample_from_derep failed.
+ * resident_stats (optional, DADA2HIP_RESIDENT_NSTATS int64 words, the finish alone): [0] bytes copied down (the rows, the host
+ * mirror, the tallies), [1] bytes copied up (the order), [2] host microseconds of the rows' download, [3] of the order, the object
+ * and the order's upload, [4] device microseconds of the kernel, [5] of the k-mer build, [6] of the mirror's download, [7] blocks
+ * the kernel was launched with (DADA2HIP_DD_SAMPLE_BLOCKS caps them), [8] uniques.  stats: dada2hip_derep_reads' words. */
+#define DADA2HIP_RESIDENT_NSTATS 16
+int dada2hip_derep_reads_resident(int64_t n, const char *seq, const char *qual, const int64_t *offsets, int64_t chunk_reads,
+                                  int32_t qual_offset, int32_t device, dada2hip_derep **out, dada2hip_sample **sample,
+                                  int64_t *stats, int64_t *resident_stats, char *errbuf, size_t errlen);
+/* The rows of a resident sample as they lie on the device, padding included (any of the four may be NULL):
+ * geometry[DADA2HIP_SAMPLE_ROWS_NGEOM] = uniques N, W2, LQ, maxlen, minlen, qmax (the largest quality byte), 0, 0;
+ * seq2[N * W2] the 2-bit words, len[N], reads[N], qual[N * LQ] the rounded quality bytes.  Ask for the geometry first. */
+#define DADA2HIP_SAMPLE_ROWS_NGEOM 8
+int dada2hip_sample_rows(dada2hip_sample *s, int32_t *geometry, uint32_t *seq2, int32_t *len, uint32_t *reads, uint8_t *qual,
+                         char *errbuf, size_t errlen);
 
 /* ---- pooling: the samples' derep objects into one (combineDereps2, R/multiSample.R:165-203; dada(pool = TRUE), R/dada.R:189-192) ----
  * A view is one sample as the accessors above expose it, or as the caller holds it.  dada2hip_derep_combine returns an ordinary
@@ -771,6 +808,21 @@ int dada2hip_filter_derep_fastq_paired(dada2hip_filter *ctx, const char *in_f, c
                                        int64_t derep_chunk_reads, int32_t derep_qual_offset, dada2hip_derep **derep_f,
                                        dada2hip_derep **derep_r, int64_t *reads_in, int64_t *reads_out, int64_t *stats,
                                        char *errbuf, size_t errlen);
+/* The same two with dada2hip_derep_reads_resident's end: every derep object comes without a quality matrix and with its resident
+ * sample.  When nothing passes, the objects and the samples are NULL and the return code is DADA2HIP_OK.  An input error of a
+ * sample fails the call: no object, no sample, no file.  resident_stats (optional): DADA2HIP_RESIDENT_NSTATS words; for a
+ * pair twice as many, the forward sample's and then the reverse sample's. */
+int dada2hip_filter_derep_fastq_resident(dada2hip_filter *ctx, const char *in, const char *out, const dada2hip_filter_params *params,
+                                         int32_t compress, int64_t chunk_reads, int64_t derep_chunk_reads, int32_t derep_qual_offset,
+                                         dada2hip_derep **derep, dada2hip_sample **sample, int64_t *reads_in, int64_t *reads_out,
+                                         int64_t *stats, int64_t *resident_stats, char *errbuf, size_t errlen);
+int dada2hip_filter_derep_fastq_paired_resident(dada2hip_filter *ctx, const char *in_f, const char *in_r, const char *out_f,
+                                                const char *out_r, const dada2hip_filter_params *params_f,
+                                                const dada2hip_filter_params *params_r, int32_t compress, int64_t chunk_reads,
+                                                int64_t derep_chunk_reads, int32_t derep_qual_offset, dada2hip_derep **derep_f,
+                                                dada2hip_derep **derep_r, dada2hip_sample **sample_f, dada2hip_sample **sample_r,
+                                                int64_t *reads_in, int64_t *reads_out, int64_t *stats, int64_t *resident_stats,
+                                                char *errbuf, size_t errlen);
 
 /* ---- filterAndTrim's orient.fwd, matchIDs, id.sep and id.field (R/filter.R:648-658, :940-1007) --------------------------------------
  * The entries above stay as they are; these take the four arguments they do not have.

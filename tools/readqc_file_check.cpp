@@ -105,6 +105,8 @@ int d2_dd_feed(void *, int64_t, const char *, const char *, const int64_t *, con
 int d2_dd_filter_chunk(dada2hip_filter *, void *, int64_t, const char *, const char *, const int64_t *, const dada2hip_filter_params *, int32_t *,
                        int32_t *, int64_t *, char *, size_t) { return DADA2HIP_ERR_DEVICE; }
 int d2_dd_finish(void *, int32_t, dada2hip_derep **, int64_t *, char *, size_t) { return DADA2HIP_ERR_DEVICE; }
+int d2_dd_finish_resident(void *, int32_t, dada2hip_derep **, dada2hip_sample **, int64_t *, int64_t *, char *, size_t) { return DADA2HIP_ERR_DEVICE; }
+void dada2hip_sample_free(dada2hip_sample *) {}
 
 }  // extern "C"
 
